@@ -10,6 +10,16 @@ Steps rotate over --batches distinct batches (different topic seeds, default 3),
 re-matches the batch the previous pass just warmed the caches with.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg 3] [--shard topics|filters]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it generates the workload, builds
+the index, settles and warms up, times the K steps and prints the line with ``metric``,
+``value``, ``unit``, ``ms_per_step`` and the run's configuration.  ``--dump-outputs DIR`` then
+also writes what the last timed step returned (``_dump_outputs``).  Everything else described
+below -- the census figures in ``config``, ``one_pass_at_a_time``, ``roofline``,
+``cpu_baseline``, ``end_to_end``, ``nif_windows``, ``nif_concurrent``, ``subscribe``,
+``crossover`` and, for N>1, the filter-sharded layout beside the replicas -- is measured only
+with ``--full``, after the timed steps and without touching their figure.
 
 N>1 is launched by the driver with torch.distributed.run (one rank per GPU).  ``--shard topics``
 (default) = every GPU holds the whole 10M-filter index and matches its own batch (weak scaling,
@@ -38,11 +48,10 @@ import sys
 import time
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+T_START = time.time()
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 
@@ -51,11 +60,33 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def _grow_heap_in_large_steps():
+    """glibc's malloc extends its heaps 128 KB at a time and trims them as they empty; drawing
+    10M filters and building their index allocates gigabytes in small nodes, and with steps of
+    256 MB and no trimming the draw took about a tenth less time.  Elsewhere: nothing."""
+    import ctypes
+    try:
+        libc = ctypes.CDLL("libc.so.6")
+        libc.mallopt(-2, 256 << 20)  # M_TOP_PAD
+        libc.mallopt(-1, 1 << 30)    # M_TRIM_THRESHOLD
+    except (OSError, AttributeError):
+        pass
+
+
 def main():
+    global torch, dist  # imported below, once the workload generator is at work
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the "
+                         "census figures, one pass at a time, the roofline's kernel timing, the "
+                         "CPU baseline, host-in/host-out, subscribe latency, the concurrent entry "
+                         "and the window sweep (N=1), the filter-sharded layout (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy "
+                         "(_dump_outputs; rank 0)")
     ap.add_argument("--settle-s", type=float, default=0.5,
                     help="untimed steps for this long before the warmup steps: the GPU's clocks "
                          "ramp over ~100 ms of load (r04: 20 timed steps after 5 warmup steps "
@@ -71,7 +102,7 @@ def main():
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="emqxgm_tune before the index is built (A/B runs), e.g. fat_buckets=0")
     ap.add_argument("--filter-shard", action="store_true",
-                    help="(default since r05) N>1: the filter-sharded layout is measured beside "
+                    help="(default since r05, with --full) N>1: the filter-sharded layout is measured beside "
                          "the replicas, after their figure is final, under a watchdog")
     ap.add_argument("--no-filter-shard", action="store_true",
                     help="N>1: leave the filter-sharded layout out")
@@ -105,21 +136,21 @@ def main():
                     help="experiment: permute the batch (outside the timed region) so that topics "
                          "of one first-two-level prefix group share an XCD shard, or fully sorted")
     args = ap.parse_args()
+    _grow_heap_in_large_steps()
+    if not args.full:
+        # a plain run measures the headline alone (the options above choose among the extras)
+        args.no_cpu_baseline = args.no_e2e = args.no_subscribe = args.no_filter_shard = True
+        args.windows = ""
+        if not args.only_nif:
+            args.nif = ""
+    if args.dump_outputs and args.shard == "filters":
+        ap.error("--dump-outputs writes a replica's result: not with --shard filters")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    # EMQXGM_DIST_BACKEND=gloo rehearses the N>1 control flow with several ranks sharing the
-    # GPUs of a smaller box (RCCL refuses two ranks on one device); production is RCCL ("nccl")
-    if world > 1:
-        dist.init_process_group(os.environ.get("EMQXGM_DIST_BACKEND", "nccl"))
-    local = local % max(1, torch.cuda.device_count())
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
 
     import workloads
-    from emqx_amd import Engine
-    from emqx_amd import dist as D
 
     nf_default, nt_default, sf, st = workloads.DEFAULTS[args.cfg]
     if args.cfg == 3:
@@ -129,28 +160,57 @@ def main():
     nf = args.filters or nf_default
     nt = args.topics or nt_default
 
-    t0 = time.time()
+    # The filters are drawn (one thread of the generator: most of a run's start-up) while torch
+    # loads and opens the device, and registered with the engine as they come: the generator
+    # draws until it has the number of distinct filters asked for, so cfg3's draws of a half, three quarters
+    # and seven eighths of them, made beside the whole draw, are its first filters (checked), ready
+    # while the rest is still drawn.  The further batches -- the same distribution under other
+    # topic seeds, no filters drawn again -- are drawn while the index is committed.  (The
+    # topics-only draw must not run beside a draw of filters; ctypes releases the GIL for each.)
+    t_gen = time.time()
     seed_t = st + (1000 * rank if args.shard == "topics" else 0)
-    w = workloads.generate(args.cfg, nf, nt, sf, seed_t)
-    # further batches: the same distribution under other topic seeds (no filters drawn again)
     nb = max(1, args.batches)
-    extra = [workloads.generate(args.cfg, nf, nt, sf, seed_t + 7919 * b, topics_only=True)
-             for b in range(1, nb)]
-    log(f"[rank {rank}] generated {w.nf} filters, {nb} x {w.nt} topics in {time.time() - t0:.1f}s")
+    heads = [nf // 2, 3 * (nf // 4), 7 * (nf // 8)] if args.cfg == 3 and nf >= 4_000_000 else []
+    parts = [_Later(lambda m=m: workloads.generate(args.cfg, m, 0, sf, seed_t)) for m in heads]
+    parts.append(_Later(lambda: workloads.generate(args.cfg, nf, nt, sf, seed_t)))
+
+    import torch
+    import torch.distributed as dist
+
+    # EMQXGM_DIST_BACKEND=gloo rehearses the N>1 control flow with several ranks sharing the
+    # GPUs of a smaller box (RCCL refuses two ranks on one device); production is RCCL ("nccl")
+    if world > 1:
+        dist.init_process_group(os.environ.get("EMQXGM_DIST_BACKEND", "nccl"))
+    local = local % max(1, torch.cuda.device_count())
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    torch.cuda.synchronize()
+
+    from emqx_amd import Engine
+    from emqx_amd import dist as D
 
     # the CPU baseline's index (reference-style ordered set) builds in the background while the
     # GPU is measured; ctypes releases the GIL, so the two do not interleave on the host
     cpu_job = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu_job = _CpuIndexJob(w, args.cfg)
+        cpu_job = _CpuIndexJob(parts[-1].result(), args.cfg)
 
     # ---- index ----
-    t0 = time.time()
-    eng, _ = _build_engine(Engine, w, np.arange(w.nf), args, local)
+    further = []
+
+    def whole_drawn(w_):
+        log(f"[rank {rank}] generated {w_.nf} filters, {w_.nt} topics in {time.time() - t_gen:.1f}s")
+        further.append(_Later(lambda: [
+            workloads.generate(args.cfg, nf, nt, sf, seed_t + 7919 * b, topics_only=True)
+            for b in range(1, nb)]))
+
+    eng, w = _build_engine_streamed(Engine, parts, args, local, whole_drawn)
     est = eng.stats()
     log(f"[rank {rank}] index: {est['n_trie_filters']} trie filters, {est['n_route_keys']} route "
         f"keys, {est['n_nodes']} nodes ({est['keyed_nodes']} token-keyed), "
-        f"{est['device_bytes'] / 2**20:.0f} MiB in {time.time() - t0:.1f}s")
+        f"{est['device_bytes'] / 2**20:.0f} MiB, {time.time() - t_gen:.1f}s after the start")
+
+    extra = further[0].result()
 
     if args.only_nif:
         out = _nif_concurrent(eng, w, args.nif)
@@ -173,12 +233,14 @@ def main():
     # S(t) as SURVEY 8d defines it (every matched prefix state) comes from a census of the
     # unpruned walk; the production walk skips leaf-only children a deeper topic cannot match
     # (CF_LEAFP), so its own loads and iterations come from a second census
-    eng.tune("leaf_prune", 0)
-    census_full = _census_mean(eng, dbat, w.nt)
-    eng.tune("leaf_prune", 1)
-    census = _census_mean(eng, dbat, w.nt)
-    census["states_visited"] = census["states"]
-    census["states"] = census_full["states"]
+    census = census_full = None
+    if args.full:
+        eng.tune("leaf_prune", 0)
+        census_full = _census_mean(eng, dbat, w.nt)
+        eng.tune("leaf_prune", 1)
+        census = _census_mean(eng, dbat, w.nt)
+        census["states_visited"] = census["states"]
+        census["states"] = census_full["states"]
 
     # pipelined steps (default): each step submits its batch and completes the previous one, so
     # two passes are in flight on the engine's two pipes (emqxgm_match_device_submit/_wait) and
@@ -188,6 +250,7 @@ def main():
     dev_inflight = min(args.inflight or eng.PIPES, eng.PIPES)
     pending = []
     turn = [0]
+    last = [None]  # the result of the step completed last (device-resident, engine-owned)
 
     def next_batch():
         b = dbat[turn[0] % nb]
@@ -196,17 +259,18 @@ def main():
 
     def step_sync():
         b_, o_, n_ = next_batch()
-        return eng.match_device(b_.data_ptr(), o_.data_ptr(), w.nt, n_)
+        last[0] = eng.match_device(b_.data_ptr(), o_.data_ptr(), w.nt, n_)
+        return last[0]
 
     def step_pipe():
         b_, o_, n_ = next_batch()
         pending.append(eng.match_device_submit(b_.data_ptr(), o_.data_ptr(), w.nt, n_))
         if len(pending) == dev_inflight:
-            eng.match_device_wait(pending.pop(0))
+            last[0] = eng.match_device_wait(pending.pop(0))
 
     def drain():
         while pending:
-            eng.match_device_wait(pending.pop(0))
+            last[0] = eng.match_device_wait(pending.pop(0))
 
     def step():
         return step_pipe() if pipelined else step_sync()
@@ -218,6 +282,9 @@ def main():
         step()
         settle_steps += 1
     drain()
+    # the settle phase ends by the clock: the rotation restarts, so that warm-up and timed steps
+    # match the same batches in every run of the same arguments
+    turn[0] = 0
     for _ in range(args.warmup):
         step()
     drain()
@@ -233,9 +300,11 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        _dump_outputs(args.dump_outputs, last[0], w.nt)
     # the same batches one pass at a time, reported beside `value` (outside the timed region)
     sync_ms = None
-    if pipelined:
+    if pipelined and args.full:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -251,35 +320,37 @@ def main():
     fsh = None
     if world > 1 and args.shard == "filters":  # the north-star layout as the headline
         fsh = _filter_sharded_run(Engine, D, args, w, dbat, rank, world, dev, local)
-    # kernel timing with HIP events on the engine's stream, in extra passes after the timed
-    # region (the events themselves add gaps between launches), one pass at a time so that a
-    # launch's duration is its own (not stretched by the other pipe's overlapping work)
-    s0 = eng.stats()
-    eng.set_profiling(True)
-    for _ in range(max(3, min(args.steps, 10))):
-        step() if not pipelined else step_sync()
-    torch.cuda.synchronize()
-    eng.set_profiling(False)
-    s1 = eng.stats()
-
-    launches = s1["tok_launches"] - s0["tok_launches"]
-    walks = s1["walk_launches"] - s0["walk_launches"]
-    tok_ms = (s1["tok_ms"] - s0["tok_ms"]) / max(1, launches)
-    exact_ms = (s1["exact_ms"] - s0["exact_ms"]) / max(1, launches)
-    walk_ms = (s1["walk_ms"] - s0["walk_ms"]) / max(1, walks)
-    pipe_ms = (s1["total_ms"] - s0["total_ms"]) / max(1, launches)
     topics_total = w.nt * world
-    compulsory = nbytes_mean + 4 * w.nt + 8 * census["pairs"]
     value = topics_total / (elapsed / args.steps)
     if args.shard == "filters" and fsh is not None:
         # the north-star layout as the headline: one batch per step over all GPUs
         topics_total, elapsed = w.nt, fsh["ms_per_step"] * 1e-3 * args.steps
         value = fsh["value"]
-    pmc = _pmc(args.cfg, w.nt, nb)
-    roofline = _roofline(w.nt, nbytes_mean, census, pmc, tok_ms, exact_ms, walk_ms, pipe_ms,
-                         exact_table_bytes=32 * int(est.get("exact_slots", 0)))
-    roofline["compulsory_bytes_per_batch"] = int(compulsory)
-    roofline["compulsory_frac"] = round(compulsory / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
+    roofline = pipe_ms = None
+    if args.full:
+        # kernel timing with HIP events on the engine's stream, in extra passes after the timed
+        # region (the events themselves add gaps between launches), one pass at a time so that a
+        # launch's duration is its own (not stretched by the other pipe's overlapping work)
+        s0 = eng.stats()
+        eng.set_profiling(True)
+        for _ in range(max(3, min(args.steps, 10))):
+            step() if not pipelined else step_sync()
+        torch.cuda.synchronize()
+        eng.set_profiling(False)
+        s1 = eng.stats()
+
+        launches = s1["tok_launches"] - s0["tok_launches"]
+        walks = s1["walk_launches"] - s0["walk_launches"]
+        tok_ms = (s1["tok_ms"] - s0["tok_ms"]) / max(1, launches)
+        exact_ms = (s1["exact_ms"] - s0["exact_ms"]) / max(1, launches)
+        walk_ms = (s1["walk_ms"] - s0["walk_ms"]) / max(1, walks)
+        pipe_ms = (s1["total_ms"] - s0["total_ms"]) / max(1, launches)
+        compulsory = nbytes_mean + 4 * w.nt + 8 * census["pairs"]
+        pmc = _pmc(args.cfg, w.nt, nb)
+        roofline = _roofline(w.nt, nbytes_mean, census, pmc, tok_ms, exact_ms, walk_ms, pipe_ms,
+                             exact_table_bytes=32 * int(est.get("exact_slots", 0)))
+        roofline["compulsory_bytes_per_batch"] = int(compulsory)
+        roofline["compulsory_frac"] = round(compulsory / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
 
     cpu = _cpu_baseline(w, args, cpu_job) if cpu_job is not None else None
     e2e = None
@@ -412,24 +483,15 @@ def main():
                 "global_batch": int(topics_total), "parallelism":
                     (f"topic-replica x{world}" if args.shard == "topics" or world == 1
                      else f"filter-shard x{world}"),
-                "pairs_per_batch": int(census["pairs"]),
                 "trie_nodes": int(est["n_nodes"]), "token_keyed_nodes": int(est["keyed_nodes"]),
-                "trie_states_per_batch": int(census["states"]),
-                "walk_states_visited_per_batch": int(census["states_visited"]),
-                "edge_slot_loads_unpruned_per_batch": int(census_full["slot_loads"]),
-                "edge_slot_loads_per_batch": int(census["slot_loads"]),
-                "walk_lane_iterations_per_batch": int(census["lane_iters"]),
-                "walk_wave_iterations_per_batch": int(census["wave_iters"]),
-                # the pruned walk's edge-bucket loads by probed level (literal / '+' probes)
-                "edge_loads_by_level": {k: [int(x) for x in v[:max(1, _last_nz(v) + 1)]]
-                                        for k, v in census["loads_by_level"].items()},
-                "pipeline_ms_per_batch": round(pipe_ms, 4),
+                **_census_config(census, census_full, pipe_ms),
                 "tune": args.tune,
                 "settle": {"seconds": args.settle_s, "untimed_steps": settle_steps},
                 "passes_in_flight": dev_inflight if pipelined else 1,
                 "one_pass_at_a_time": (None if sync_ms is None else {
                     "value": round(topics_total / (sync_ms * 1e-3), 1), "ms_per_step": round(sync_ms, 4)}),
-                "pairs_per_s": round(census["pairs"] * (topics_total / w.nt) / (elapsed / args.steps), 1),
+                **({} if census is None else {"pairs_per_s": round(
+                    census["pairs"] * (topics_total / w.nt) / (elapsed / args.steps), 1)}),
                 "filter_sharded": fsh,
             },
             "roofline": roofline,
@@ -453,6 +515,93 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+    log(f"[rank {rank}] line printed {time.time() - T_START:.1f}s after the start")
+
+
+DUMP_ROWS = 1 << 20       # topics whose rows --dump-outputs writes at most
+DUMP_MAX_BYTES = 64 << 20  # all files of one dump together
+
+
+def _dump_outputs(path, d, nt):
+    """What the last timed step returned (emqxgm_dev_out d, read back from HBM), as .npy files
+    under path, for comparing two builds output for output:
+
+      n_pairs.npy    f64 [1]   the batch's matched (topic, filter) pairs
+      topics.npy     f64 [k]   the topics written: all of them, or a fixed sample (generator
+                               seeded with 0, ascending) of DUMP_ROWS, halved until the files
+                               fit DUMP_MAX_BYTES
+      row_len.npy    f32 [k]   trie filters matched by each of those topics
+      filter_id.npy  f64 [sum] their rows one after another; a row is a set (the walk stages its
+                               pairs in no fixed order), so each is written ascending
+      exact_id.npy   f64 [k]   the route key equal to the topic (4294967295 = none)
+      n_words.npy    f32 [k]   the topic's levels
+    """
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+
+    def host(ptr, n, what):
+        a = np.full(n, 0xFFFFFFFF, np.uint32)
+        if n and ptr:
+            rc = hip.hipMemcpy(a.ctypes.data, ptr, 4 * n, 2)  # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise RuntimeError(f"--dump-outputs: hipMemcpy of {what} failed: {rc}")
+        return a
+
+    if d is None or d.n != nt:
+        raise RuntimeError("--dump-outputs: no result of a timed step")
+    _write_outputs(path, host(d.row_ptr, nt + 1, "row_ptr"), host(d.filter_id, d.n_pairs, "filter_id"),
+                   host(d.exact_id, nt, "exact_id"), host(d.n_words, nt, "n_words"))
+
+
+def _write_outputs(path, row_ptr, filter_id, exact_id, n_words):
+    """_dump_outputs' files from a batch's result on the host (u32 arrays)."""
+    nt = len(row_ptr) - 1
+    row = row_ptr.astype(np.int64)
+    if int(row[-1]) != len(filter_id) or np.any(np.diff(row) < 0):
+        raise RuntimeError("--dump-outputs: the row pointers do not describe the batch's pairs")
+    k = min(nt, DUMP_ROWS)
+    while True:
+        sel = (np.arange(nt) if k == nt else
+               np.sort(np.random.default_rng(0).choice(nt, k, replace=False)))
+        lens = row[sel + 1] - row[sel]
+        # (.npy: a header of 128 bytes per file at these sizes)
+        if 24 * k + 8 * int(lens.sum()) + 8 + 6 * 128 <= DUMP_MAX_BYTES or k <= 1:
+            break
+        k //= 2
+    first = np.cumsum(lens) - lens
+    pos = np.repeat(row[sel] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    ids = filter_id[pos]
+    ids = ids[np.lexsort((ids, np.repeat(np.arange(k), lens)))]
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("n_pairs", np.array([len(filter_id)], np.float64)),
+                    ("topics", sel.astype(np.float64)), ("row_len", lens.astype(np.float32)),
+                    ("filter_id", ids.astype(np.float64)),
+                    ("exact_id", exact_id[sel].astype(np.float64)),
+                    ("n_words", n_words[sel].astype(np.float32))):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+class _Later:
+    """fn() on a thread of its own; result() waits for it and raises what it raised."""
+
+    def __init__(self, fn):
+        import threading
+        self.out = self.err = None
+
+        def run():
+            try:
+                self.out = fn()
+            except BaseException as e:  # handed to the caller of result()
+                self.err = e
+        self.th = threading.Thread(target=run, daemon=True)
+        self.th.start()
+
+    def result(self):
+        self.th.join()
+        if self.err is not None:
+            raise self.err
+        return self.out
 
 
 WATCHDOG_EXIT = 3  # the rank's exit status when the N>1 watchdog ends it
@@ -511,6 +660,41 @@ def _build_engine(Engine, w, idx, args, local):
     gid[tid] = idx[wsel]
     eng.commit()
     return eng, gid
+
+
+def _build_engine_streamed(Engine, parts, args, local, whole_drawn):
+    """_build_engine over every filter of a workload that arrives in parts: draws of growing
+    size (_Later), each beginning with the filters of the one before (checked).  A part's new
+    filters are registered when it is there -- per table the calls see the filters in the order
+    in which _build_engine hands them over in one piece, so ids and index are the same -- and the
+    index is committed after the last part, the whole workload; whole_drawn(it) is called as soon
+    as it is there.  Returns (engine, workload)."""
+    eng = Engine(device=local, walk_wg_per_cu=args.wg_per_cu)
+    for kv in args.tune:
+        k, v = kv.split("=", 1)
+        eng.tune(k, int(v))
+    done, w, t0 = 0, None, time.time()
+    for i, part in enumerate(parts):
+        p = part.result()
+        t_there = time.time() - t0
+        if i == len(parts) - 1:
+            whole_drawn(p)
+        if w is not None and not (np.array_equal(p.foff[:done + 1], w.foff)
+                                  and np.array_equal(p.fbytes[:len(w.fbytes)], w.fbytes)
+                                  and np.array_equal(p.fwild[:done], w.fwild)):
+            raise RuntimeError(f"the draw of {w.nf} filters is not the head of the draw of {p.nf}")
+        w = p
+        fb = w.fbytes[int(w.foff[done]):]
+        fo = w.foff[done:] - w.foff[done]
+        if not args.no_route_keys:
+            eng.route_ref_many(fb, fo)
+        wb, wo = _subset_packed(fb, fo, np.nonzero(w.fwild[done:])[0])
+        eng.trie_insert_many(wb, wo)
+        log(f"filters {done}..{w.nf}: drawn {t_there:.1f}s, registered {time.time() - t0:.1f}s "
+            f"after the engine's start")
+        done = w.nf
+    eng.commit()
+    return eng, w
 
 
 def _window_sweep(Batcher, eng, w, sizes):
@@ -710,6 +894,25 @@ def _subscribe_latency(eng, w, n_idle=400, max_build_s=30.0):
                                    build_ms=round(s1["last_build_ms"], 1),
                                    waited_for_build=int(s1["bg_waits"] - s0["bg_waits"]),
                                    catchup_changes=int(s1["catchup_changes"]))}
+
+
+def _census_config(census, census_full, pipe_ms):
+    """config's figures from the census passes and the profiled passes (--full), else none."""
+    if census is None:
+        return {}
+    return {
+        "pairs_per_batch": int(census["pairs"]),
+        "trie_states_per_batch": int(census["states"]),
+        "walk_states_visited_per_batch": int(census["states_visited"]),
+        "edge_slot_loads_unpruned_per_batch": int(census_full["slot_loads"]),
+        "edge_slot_loads_per_batch": int(census["slot_loads"]),
+        "walk_lane_iterations_per_batch": int(census["lane_iters"]),
+        "walk_wave_iterations_per_batch": int(census["wave_iters"]),
+        # the pruned walk's edge-bucket loads by probed level (literal / '+' probes)
+        "edge_loads_by_level": {k: [int(x) for x in v[:max(1, _last_nz(v) + 1)]]
+                                for k, v in census["loads_by_level"].items()},
+        "pipeline_ms_per_batch": round(pipe_ms, 4),
+    }
 
 
 def _census_mean(eng, dbat, nt):

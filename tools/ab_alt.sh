@@ -2,7 +2,7 @@
 # GPU box: bash tools/ab_alt.sh TAG V C N
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; V=$2; C=$3; N=${4:-3}; mkdir -p $O
-A="--no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10"
+A="--full --no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10"
 cp $R/emqx_amd/libemqx_gpumatch.so $O/base.so || exit 1
 for i in $(seq $N); do
   for v in base $V; do

@@ -9,7 +9,7 @@ cp $R/emqx_amd/libemqx_gpumatch.so $R/ablib/lib_base.so || exit 1
 for i in 1 2 3; do
   for v in base $V; do
     cp $R/ablib/lib_$v.so $R/emqx_amd/libemqx_gpumatch.so || exit 1
-    (cd $R && timeout -k 10 300 python -u bench.py --cfg 3 --no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10) > $O/${v}_c3_r$i.json 2> $O/${v}_r$i.log || { cp $R/ablib/lib_base.so $R/emqx_amd/libemqx_gpumatch.so; exit 1; }
+    (cd $R && timeout -k 10 300 python -u bench.py --cfg 3 --full --no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10) > $O/${v}_c3_r$i.json 2> $O/${v}_r$i.log || { cp $R/ablib/lib_base.so $R/emqx_amd/libemqx_gpumatch.so; exit 1; }
     echo "[ab] $v $i done"
   done
 done

@@ -3,7 +3,7 @@
 set -o pipefail
 cd /root/repo
 O=gpurun_out/${TAG:-xab1}; mkdir -p $O
-B="--no-cpu-baseline --no-e2e --nif= --no-subscribe"
+B="--full --no-cpu-baseline --no-e2e --nif= --no-subscribe"
 timeout -k 10 900 python -u -m pytest tests/test_gpu_parity.py -x -v --timeout 300 --timeout-method thread > $O/parity.log 2>&1 || { tail -30 $O/parity.log; exit 1; }
 tail -1 $O/parity.log
 bash tools/job.sh ${TAG:-xab1} ab=2:0,4:0,3:0/xglob || exit 1

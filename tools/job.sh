@@ -39,7 +39,7 @@ shift
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 KRE="k_walk|k_tok|k_exact|k_scatter|k_verify|k_scan"
-NOCPU="--no-cpu-baseline --no-e2e --nif="
+NOCPU="--full --no-cpu-baseline --no-e2e --nif="
 PROF="$NOCPU --settle-s 0 --no-subscribe"  # profiled runs: every launch is profiled, so no settle phase
 
 step_tests() {
@@ -64,7 +64,7 @@ step_bench() {
   local T=""; [ -n "$topics" ] && [ "$topics" != 0 ] && T="--topics $topics"
   local tag=${extra//[^a-zA-Z0-9=]/_}
   local name=bench_c${cfg}_${topics:-0}${tag:+_$tag}
-  (cd $R && timeout -k 10 900 python -u bench.py --cfg $cfg $T ${extra//,/ }) > $O/$name.json 2> $O/$name.log
+  (cd $R && timeout -k 10 900 python -u bench.py --full --cfg $cfg $T ${extra//,/ }) > $O/$name.json 2> $O/$name.log
 }
 
 step_onepass() {
@@ -173,7 +173,7 @@ step_dist() {
   [ "$1" = filters ] && extra="--shard filters"
   [ "$1" = both ] && extra="--filter-shard"
   (cd $R && EMQXGM_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 $extra \
+    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --full $extra \
     --steps 5 --warmup 1) > $O/dist_n2${1:+_$1}.json 2> $O/dist_n2${1:+_$1}.log
 }
 

@@ -4,7 +4,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pipe_sweep; mkdir -p $O
-A="--no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10"
+A="--full --no-cpu-baseline --no-e2e --nif= --no-subscribe --steps 100 --warmup 10"
 for w in 3 2 4 3; do
   (cd $R && timeout -k 10 300 python -u bench.py $A --tune walk_wg_per_cu_pipe=$w > $O/wg$w.$RANDOM.json 2> $O/wg$w.log) || exit 1
 done

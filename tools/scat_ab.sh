@@ -1,7 +1,7 @@
 set -o pipefail
 cd /root/repo
 O=gpurun_out/${TAG:-scat1}; mkdir -p $O
-B="--no-cpu-baseline --no-e2e --nif= --no-subscribe"
+B="--full --no-cpu-baseline --no-e2e --nif= --no-subscribe"
 timeout -k 10 900 python -u -m pytest tests/test_gpu_parity.py -x -v --timeout 300 --timeout-method thread > $O/parity.log 2>&1 || { tail -30 $O/parity.log; exit 1; }
 tail -2 $O/parity.log
 for i in 1 2; do

@@ -4,7 +4,7 @@ set -o pipefail
 cd /root/repo
 bash tools/job.sh scat3 stall=2:k_scatter_grp prof=2 || exit 1
 O=gpurun_out/scat3
-B="--no-cpu-baseline --no-e2e --nif= --no-subscribe"
+B="--full --no-cpu-baseline --no-e2e --nif= --no-subscribe"
 for i in 1 2; do
   for v in grp direct; do
     if [ $v = direct ]; then export EMQXGM_SCATTER_DIRECT=1; else unset EMQXGM_SCATTER_DIRECT; fi

@@ -1,7 +1,7 @@
 """Per-wave timeline of one census walk (diagnostic).
 
-GPU box:  EMQXGM_WAVE_TIMES=gpurun_out/wt.bin python bench.py --steps 1 ...
-          python tools/wave_times.py gpurun_out/wt.bin
+On the GPU:  EMQXGM_WAVE_TIMES=wt.bin python bench.py --full --steps 1 ...
+             python tools/wave_times.py wt.bin
 Each wave records {start, claims exhausted, end} with wall_clock64() (100 MHz).
 """
 import sys
