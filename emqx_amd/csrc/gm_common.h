@@ -114,10 +114,20 @@ constexpr uint32_t FAT_MAX_DEPTH = 6;  // C's word (level depth(C)) is a record 
 // class summary of the child's literal children's level tokens (class = sig_bit(token)); the
 // walk does not probe a literal child whose token's class bit is clear.  Bits are only ever
 // added (a delta commit ORs a new child in, deletions leave them), so a clear bit is exact.
+// Lent signatures: a child C without literal children (CF_LIT clear in cf) has no use for the
+// field, so it holds the signature of C's '+' child instead (0: C has none) -- the carried
+// '+' child p has no bits to spare in p.cf, and the walk, which creates p's state without a probe,
+// drops the literal probe under p when the next word's class bit is clear (cfg3: the k of
+// site/S/device/D/+/k under a device D that has only '+' below it).  With CF_LIT set the field
+// is C's own (0: keyed, below).  The same rule holds for a fat half's word (FAT_ID | field), the
+// root's half in the kernel arguments and the root's own signature.  A reader that ignores lent
+// bits is still exact: they only ever drop probes that find nothing.
 constexpr uint32_t SIG_SHIFT = CF_ID_BITS;
-GM_HD uint32_t sig_bit(uint64_t tok) {
-  return 1u << (uint32_t)(((((tok * 0x9E3779B97F4A7C15ull) >> 32) & 0xFFFFFFFFull) * 6ull) >> 32);
+constexpr uint32_t SIG_CLASSES = 6;
+GM_HD uint32_t sig_class(uint64_t tok) {
+  return (uint32_t)(((((tok * 0x9E3779B97F4A7C15ull) >> 32) & 0xFFFFFFFFull) * SIG_CLASSES) >> 32);
 }
+GM_HD uint32_t sig_bit(uint64_t tok) { return 1u << sig_class(tok); }
 // Depth code h of the child C (bits CF_H0 | CF_H1 = h & 1, h & 2): every filter strictly below
 // C ends within h levels of C and none of them is a '#' filter, so a topic with more than h
 // words left after C cannot match anything below it and the walk does not expand C's children.

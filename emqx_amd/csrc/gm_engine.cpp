@@ -305,11 +305,19 @@ struct TrieModel {
     return cf_with_depth_code(f, hcode[i]);
   }
   uint32_t hfd(uint32_t i) const { return hf[i]; }  // id, LIST_MULTI | multi index, or NONE
+  // The signature field of c's slot (gm_common.h "Child signature"): c's own literal children's
+  // classes, 0 for a keyed node with literal children (the keyed flag) -- and, when c has no
+  // literal child (CF_LIT clear, its own signature unused), the classes of the literal children
+  // of c's '+' child, lent to the walk (a keyed node that lost its last literal child lends
+  // them too: a 0 there would rule out every child of the '+' node).  A '+' node is never keyed.
+  uint32_t sig_field(uint32_t c) const {
+    if (nlit[c]) return keyed[c] ? 0u : (uint32_t)sig[c];
+    return pchild[c] ? (uint32_t)sig[pchild[c]] : 0u;
+  }
   void node_slot(uint32_t c, uint4* sl) const {  // the 2 x uint4 of c's incoming edge
     const uint32_t p = pchild[c];
     sl[0] = make_uint4((uint32_t)tok[c], (uint32_t)(tok[c] >> 32),
-                       (half[c] ? FAT_ID : parent[c]) | ((keyed[c] ? 0u : (uint32_t)sig[c]) << SIG_SHIFT),
-                       cf(c));
+                       (half[c] ? FAT_ID : parent[c]) | (sig_field(c) << SIG_SHIFT), cf(c));
     sl[1] = make_uint4(hfd(c), tw[c], p ? pcf(p) : 0u, p ? phf(p) : NONE);
   }
   // the carried copy of '+' child p (gm_common.h CF_PTW): its '#' filter, or -- when it has
@@ -472,6 +480,7 @@ struct emqxgm {
   WalkGeom geom_pipe;
   uint32_t pipe_wg_per_cu = 3;
   uint32_t leafp_mask = CF_HMASK;  // depth-code pruning (tune "leaf_prune")
+  uint32_t psig_off = 0;           // 0x3F: the walk ignores lent signatures (tune "plus_sig" 0)
   uint64_t census_depth[2 * CENSUS_DEPTHS] = {};  // the last census pass's loads per level
   uint8_t* d_in_bytes = nullptr;
   uint32_t* d_in_off = nullptr;
@@ -1142,7 +1151,7 @@ int upload_tables(emqxgm* h, const BuildIn& in, TrieModel& m, DevIndex& nx, Owne
   nx.xwmask = m.xcap_w - 1;
   const uint32_t root_p = m.pchild[0];
   nx.root_cf = m.cf(0);
-  nx.root_sig = m.sig[0];
+  nx.root_sig = m.sig_field(0);
   nx.root_hf = m.hfd(0);
   nx.root_pcf = root_p ? m.pcf(root_p) : 0u;
   nx.root_phf = root_p ? m.phf(root_p) : NONE;
@@ -1170,6 +1179,7 @@ void set_tables(DevIndex& to, const DevIndex& from) {
   x.foff = to.foff;
   x.fver = to.fver;
   x.leafp_mask = to.leafp_mask;
+  x.psig_off = to.psig_off;
   to = x;
 }
 
@@ -1763,7 +1773,9 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
   }
 
   // ---- patch lists: a dirty node rewrites its own slot, and its parent's slot when it is the
-  // parent's '+' child (the parent's slot carries its {cf, hf}) ----
+  // parent's '+' child (the parent's slot carries its {cf, hf}, and lends its signature when
+  // the parent has no literal child: sig_field -- a '+' node that gains a literal child is
+  // dirty, so the lent bits follow in the same commit) ----
   std::sort(dirty.begin(), dirty.end());
   dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
   std::vector<uint32_t> tn_nodes;
@@ -1800,7 +1812,7 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
   DevIndex& ix = h->ix;
   const uint32_t root_p = m.pchild[0];
   ix.root_cf = m.cf(0);
-  ix.root_sig = m.sig[0];
+  ix.root_sig = m.sig_field(0);
   ix.root_hf = m.hfd(0);
   ix.root_pcf = root_p ? m.pcf(root_p) : 0u;
   ix.root_phf = root_p ? m.phf(root_p) : NONE;
@@ -2412,6 +2424,7 @@ int pass_enqueue(emqxgm* h, PassCtx& c, const Epoch& E, const uint8_t* d_bytes,
   hipStream_t st = c.stream;
   DevIndex ix = E.ix;
   ix.leafp_mask = h->leafp_mask;
+  ix.psig_off = h->psig_off;
   // the epoch's uploads / patches must have landed (a full build's have: its wait is skipped)
   if (!E.ready_seen.load(std::memory_order_relaxed)) {
     if (hipEventQuery(E.ready) == hipSuccess)
@@ -4858,6 +4871,12 @@ int emqxgm_tune(emqxgm_t* h, const char* key, int64_t value) {
     if (value < 0 || value > 1) return -EINVAL;
     std::lock_guard<std::mutex> g(h->mmu);
     h->leafp_mask = value ? CF_HMASK : 0u;
+    return 0;
+  }
+  if (strcmp(key, "plus_sig") == 0) {  // 1 (default): lent signatures filter carried '+' children
+    if (value < 0 || value > 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->psig_off = value ? 0u : 0x3Fu;
     return 0;
   }
   if (strcmp(key, "spin_us") == 0) {  // host pipes' waits poll before they block

@@ -42,6 +42,7 @@ struct DevIndex {
   bool wild_empty = true;          // no committed wildcard route key
   bool needs_verify = false;        // some trie filter has a hashed (long or test) token
   uint32_t leafp_mask = (1u << 26) | (1u << 29);  // CF_HMASK: depth-code pruning (0: off)
+  uint32_t psig_off = 0;  // 0x3F: lent signatures (gm_common.h) are not used by the walk (A/B)
 };
 
 // Layout of the staged pairs of one pass.  Wide: {topic, filter, rank | REJ_BIT}, 12 B.  Packed

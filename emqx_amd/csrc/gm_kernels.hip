@@ -787,6 +787,7 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
   a.static_claim = 1;
   a.census = census;
   a.leafp_mask = ix.leafp_mask;
+  a.psig_off = ix.psig_off;
   a.root_sig = ix.root_sig;
   a.rh0 = ix.rh0;
   a.rh1 = ix.rh1;

@@ -66,6 +66,7 @@ struct WalkArgs {
   uint32_t lanes;
   uint32_t tblk;        // topics claimed per wave per atomic (smaller for small batches)
   uint32_t leafp_mask;  // CF_HMASK (depth-code pruning, gm_common.h) or 0
+  uint32_t psig_off;    // 0, or 0x3F: lent signatures pass every class (tune "plus_sig" 0)
   uint32_t stat_chunks; // waves owning a static first chunk of staged pairs (chunk = wave), or 0
   uint32_t static_claim;  // 1: k_tok started the claim counters past each wave's first block
   uint32_t static_one;  // 1: at most one topic per lane of the grid -- lane gl walks topic gl,
@@ -132,10 +133,12 @@ template <bool PKO = false>
 __device__ __forceinline__ void put(uint32_t i, uint32_t t, uint32_t f, uint32_t r,
                                     const WalkArgs& A) {
   if (i >= A.pcap) return;
-  // (the walk's ranks carry no reject bit, and one past the rank field only ever lands in a
-  // pass that CTL_PKOVF redoes wide: no masking here)
+  // (the walk's ranks carry no reject bit.  A rank past the field is masked: unmasked it would
+  // carry into the filter id, which k_verify and k_scatter use as an index before the host sees
+  // CTL_PKOVF and redoes the pass wide)
   if (PKO || A.fmt.pk)  // (wave-uniform)
-    ((uint64_t*)A.stg)[i] = ((uint64_t)t << A.fmt.tsh) | ((uint64_t)f << A.fmt.fsh) | ((uint64_t)r << 1);
+    ((uint64_t*)A.stg)[i] = ((uint64_t)t << A.fmt.tsh) | ((uint64_t)f << A.fmt.fsh) |
+                            ((uint64_t)(r & A.fmt.rmask) << 1);
   else
     A.stg[i] = make_uint3(t, f, r);
 }
@@ -172,6 +175,7 @@ struct Lane {
   uint32_t tcol;  // the s_tw column of the lane's topic (its own; a pair's: the leading lane's)
   uint32_t n, fl, sp, ne;
   uint32_t np;  // entries of s_em[0, min(ne, EMX)) that are plain ids (not multi[] lists)
+  uint32_t cls; // sig_class of the topic's record tokens, 3 bits per level (set at activation)
   bool overflow;
 };
 
@@ -265,13 +269,20 @@ __device__ __forceinline__ void visit(Lane& L, typename ItemT<CPT>::type (*s_stk
 // `plus_ok` = false drops the '+' child (the root of a '$' topic, emqx_trie.erl:282-289).
 // `sig` = the state's child signature (gm_common.h sig_bit): when word d's class bit is clear no
 // literal child can match it, so the literal probe is dropped (a select on CF_LIT).  Levels
-// past the record's tokens are not filtered.
+// past the record's tokens are not filtered.  With CF_LIT clear in `cf` the field is lent to the
+// carried '+' child (gm_common.h): it summarises that child's literal children, and the literal
+// probe under it is dropped the same way when word d+1's class bit is clear.
 // `fat`: the state's only literal child G comes with it (gm_common.h FAT_ID: the second half of
 // the state's bucket, or the root's half in the arguments), {h0, h1} = G's slot.  Its literal
 // children are then never probed by hash: G's state is created here, in the same round trip,
 // when word d equals G's token (fat states have d <= FAT_MAX_DEPTH < REC_TOKS), and nothing is
 // when it does not.
-template <bool SPILL, uint32_t STK, bool CPT, bool FAT = false>
+// LENT = false compiles the lent-signature filter out and keeps r06's per-state code (the own
+// filter from a sig_bit of the token): the pair walk, which runs where the walk is bound by its
+// instruction count (small batches, indexes whose walks outgrow a lane's stack: cfg1, cfg2), lost
+// 1-2% to the filter's instructions in every form measured (MEASUREMENTS r07) and meets few
+// such probes; the one-lane-per-topic walks and the census have it.
+template <bool SPILL, uint32_t STK, bool CPT, bool FAT = false, bool LENT = true>
 __device__ __forceinline__ void create(Lane& L, typename ItemT<CPT>::type (*s_stk)[WG], uint32_t (*s_em)[WG],
                                        const uint64_t (*s_tw)[WG], const WalkArgs& A,
                                        uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig,
@@ -282,18 +293,31 @@ __device__ __forceinline__ void create(Lane& L, typename ItemT<CPT>::type (*s_st
   // a keyed state (CF_LIT with signature 0, gm_common.h edge_home): its children are placed by
   // token and not summarised by class
   const bool keyed = sig == 0u && (cf & CF_LIT);
+  // the carried '+' child's signature (from the unstripped cf): lent, or unknown (every class)
+  const uint32_t lent = ((cf & CF_LIT) ? 0x3Fu : sig) | A.psig_off;
   cf = leaf_strip(A.leafp_mask, L.n, cf, d);
-  const uint64_t wtok = s_tw[d < REC_TOKS ? d : REC_TOKS - 1][L.tcol];
   // a fat state's literal child: its token against word d (exact), else the signature filter
+  const uint64_t wtok = s_tw[d < REC_TOKS ? d : REC_TOKS - 1][L.tcol];
   const bool fat_go = fat && (cf & CF_LIT) && d < L.n && d < REC_TOKS &&
                       (uint32_t)wtok == h0.x && (uint32_t)(wtok >> 32) == h0.y;
-  cf = (fat || (!keyed && d < REC_TOKS && !(sig & sig_bit(wtok)))) ? (cf & ~CF_LIT) : cf;
+  // sig_bit of words d and d+1, from the classes computed once per topic (a sig_bit per state
+  // is two multiplies); past the record's tokens the classes read 0 and the filters below do
+  // not apply
+  const uint32_t cw = L.cls >> (3u * min(d, REC_TOKS));
+  const uint32_t wbit = LENT ? 1u << (cw & 7u) : sig_bit(wtok), pbit = 1u << ((cw >> 3) & 7u);
+  cf = (fat || (!keyed && d < REC_TOKS && !(sig & wbit))) ? (cf & ~CF_LIT) : cf;
   pcf = leaf_strip(A.leafp_mask, L.n, pcf, d + 1);
+  // The carried '+' child at depth d+1 loses its literal probe when word d+1's class is not
+  // among its literal children's (a select, as above).  No `d + 1 < n` guard is needed: this
+  // function returns before it expands the carried child when d >= n, and at d + 1 == n
+  // visit() takes its `d == n` branch and never looks at CF_LIT (word n's token reads 0).  A
+  // change to either must bring the guard back.
+  if constexpr (LENT) pcf = (d + 1 < REC_TOKS && !(lent & pbit)) ? (pcf & ~CF_LIT) : pcf;
   visit<SPILL, STK, CPT>(L, s_stk, s_em, A, cf, hf, tw, d, lit, keyed ? IT_KEYED : 0u);
   states += 1;
   if (FAT && fat_go)
-    create<SPILL, STK, CPT, false>(L, s_stk, s_em, s_tw, A, h0.w, h1.x, h1.y, h0.z >> SIG_SHIFT, h1.z,
-                              h1.w, d + 1, true, true, states);
+    create<SPILL, STK, CPT, false, LENT>(L, s_stk, s_em, s_tw, A, h0.w, h1.x, h1.y, h0.z >> SIG_SHIFT,
+                                         h1.z, h1.w, d + 1, true, true, states);
   if (!plus_ok || d >= L.n || !(cf & CF_PLUS)) return;
   const bool ptw = (pcf & CF_PTW) != 0;
   if (d + 1 == L.n && (pcf & CF_TW) && !ptw) {
@@ -355,6 +379,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
   L.sp = 0;
   L.ne = 0;
   L.np = 0;
+  L.cls = 0;
   L.overflow = false;
   // topic context (t = NONE: idle) and the next topic, its record prefetched ahead
   uint32_t t = NONE, wb = 0, rank = 0;
@@ -418,18 +443,22 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         A.cnt[t] = 0;
         t = NONE;
       } else {
-        s_tw[0][L.tcol] = ((uint64_t)nr0.w << 32) | nr0.z;
-        s_tw[1][L.tcol] = ((uint64_t)nr1.y << 32) | nr1.x;
-        s_tw[2][L.tcol] = ((uint64_t)nr1.w << 32) | nr1.z;
-        s_tw[3][L.tcol] = ((uint64_t)nr2.y << 32) | nr2.x;
-        s_tw[4][L.tcol] = ((uint64_t)nr2.w << 32) | nr2.z;
-        s_tw[5][L.tcol] = ((uint64_t)nr3.y << 32) | nr3.x;
-        s_tw[6][L.tcol] = ((uint64_t)nr3.w << 32) | nr3.z;
+        const uint64_t tk[REC_TOKS] = {
+            ((uint64_t)nr0.w << 32) | nr0.z, ((uint64_t)nr1.y << 32) | nr1.x,
+            ((uint64_t)nr1.w << 32) | nr1.z, ((uint64_t)nr2.y << 32) | nr2.x,
+            ((uint64_t)nr2.w << 32) | nr2.z, ((uint64_t)nr3.y << 32) | nr3.x,
+            ((uint64_t)nr3.w << 32) | nr3.z};
+        L.cls = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < REC_TOKS; ++k) {
+          s_tw[k][L.tcol] = tk[k];
+          if constexpr (!PAIR) L.cls |= sig_class(tk[k]) << (3u * k);  // (create's LENT)
+        }
         const bool dollar = (L.fl & T_DOLLAR) != 0;
         // the root: no root '#' and no root '+' for a '$' topic (emqx_trie.erl:282-289); a
         // pair's root state is its leading lane's (the partner takes items from it)
         if (lead)
-          create<SPILL, STK, CPT, true>(L, s_stk, s_em, s_tw, A, A.root_cf, dollar ? NONE : A.root_hf, NONE,
+          create<SPILL, STK, CPT, true, !PAIR>(L, s_stk, s_em, s_tw, A, A.root_cf, dollar ? NONE : A.root_hf, NONE,
                         A.root_sig, A.root_pcf,
                         A.root_phf, 0, !dollar, false, c_states,
                         (A.rh0.z & CF_ID_MASK) == FAT_ID, A.rh0, A.rh1);
@@ -715,7 +744,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         const uint32_t csig = (ha ? a0.z : b0.z) >> SIG_SHIFT;
         // a fat node sits in the first half of its bucket, its only literal child in the second
         const bool fat = ha && (b0.z & CF_ID_MASK) == FAT_ID;
-        create<SPILL, STK, CPT, true>(L, s_stk, s_em, s_tw, A, ccf, chf, ctw, csig, cpcf, cphf, p.k + 1,
+        create<SPILL, STK, CPT, true, !PAIR>(L, s_stk, s_em, s_tw, A, ccf, chf, ctw, csig, cpcf, cphf, p.k + 1,
                                  true, (p.cur & IT_KIND) != IT_PLUS, c_states, fat, b0, b1);
       } else if (a0.z == NONE || b0.z == NONE) {
         p.busy = false;

@@ -670,7 +670,13 @@ int emqxgm_walk_census_levels(emqxgm_t* h, uint64_t* out, uint32_t n_out);
 
 int emqxgm_set_profiling(emqxgm_t* h, int on);
 /* Runtime tuning knobs: "walk_wg_per_cu" (persistent walk workgroups per CU); "leaf_prune"
- * (1 default: depth-code pruning in the walk, 0 off); "host_out" (host pipes copy results to the
+ * (1 default: depth-code pruning in the walk, 0 off); "plus_sig" (1 default: the walk drops the
+ * literal probe under a carried '+' child whose lent signature rules the next word
+ * out; 0: lent signatures are ignored, an A/B -- from the next pass on, no rebuild; the pair walk
+ * is built without this filter: it runs batches of at most half the walk grid's
+ * lanes, every batch of an index whose walks outgrew a lane's shallow stack, and every batch at
+ * "walk_pair" 2; emqxgm_walk_census always runs a one-lane walk with the filter, so for such
+ * passes it counts slightly fewer loads than the production kernel issues); "host_out" (host pipes copy results to the
  * host with hipMemcpyAsync, 0 default, or with a kernel writing host memory, 1);
  * "walk_pair" (1 default: a batch of at most half the walk grid's lanes is walked by two lanes
  * per topic; 0: one lane per topic); "exact_range_kb" (0 default: one route-key probe pass over the whole table; > 0: the probe
