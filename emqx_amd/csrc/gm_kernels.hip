@@ -13,6 +13,7 @@
 
 #include "gm_common.h"
 #include "gm_kernels.h"
+#include "gm_match.h"
 
 namespace gm {
 
@@ -52,47 +53,7 @@ __device__ __forceinline__ uint32_t mbcnt64(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-template <class PA, class PB>
-__device__ __forceinline__ bool bytes_equal(PA a, PB b, uint32_t len) {
-  for (uint32_t i = 0; i < len; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
-}
-
-// emqx_topic:match/2 (emqx_topic.erl:67-89) on raw bytes.  T and F are byte accessors over LDS
-// or global memory.  A '+'/'#' word of T is compared literally, as match/2 does for wildcard
-// names.  DOLLAR: the binary clauses (:70-73, a '$' name never matches a root wildcard); false
-// for match/2 called on word lists, which skips them (emqx_authz_rule.erl:213-214).
-template <bool DOLLAR = true, class PT, class PF>
-__device__ __forceinline__ bool mqtt_match(PT T, uint32_t tl, PF F, uint32_t fl) {
-  if (DOLLAR && tl > 0 && T[0] == '$' && fl > 0 && (F[0] == '+' || F[0] == '#')) return false;
-  uint32_t i = 0, j = 0;  // start of the current topic / filter word
-  for (;;) {
-    uint32_t je = j;
-    while (je < fl && F[je] != '/') ++je;
-    const bool flast = (je == fl);
-    const uint32_t flen = je - j;
-    const bool fplus = (flen == 1 && F[j] == '+');
-    const bool fhash = (flen == 1 && F[j] == '#');
-    if (fhash && flast) return true;  // match(_, ['#']) -> true
-    if (i > tl) return false;         // match([], [_|_]) -> false
-    uint32_t ie = i;
-    while (ie < tl && T[ie] != '/') ++ie;
-    bool eq = fplus;
-    if (!eq && flen == ie - i) {
-      eq = true;
-      for (uint32_t q = 0; q < flen; ++q)
-        if (T[i + q] != F[j + q]) {
-          eq = false;
-          break;
-        }
-    }
-    if (!eq) return false;
-    i = ie + 1;
-    j = je + 1;
-    if (flast) return i > tl;  // match([], []) -> true ; match([_|_], []) -> false
-  }
-}
+// (bytes_equal and mqtt_match, emqx_topic:match/2 on raw bytes: gm_match.h)
 
 // ----------------------------------------------------------------------------------------
 // exclusive scan (u32), reduce-then-scan over tiles of SCAN_TILE elements
