@@ -269,6 +269,11 @@ struct TrieModel {
   std::vector<uint32_t> fchild;
   std::vector<uint8_t> half;
   std::vector<uint8_t> keyed;  // the node's children are placed by token (gm_common.h edge_home)
+  // the only literal child of a depth-2 '+' node (G/+ for a first-level node G), kept while that
+  // node has exactly one: set when its nlit becomes 1, dropped when it becomes 2 or a literal
+  // child goes (after a deletion back to one it stays absent until the next full build; absent
+  // is always correct).  Feeds root_plus_half; not part of a snapshot (lone_rebuild).
+  std::unordered_map<uint32_t, uint32_t> lone;
   std::vector<uint64_t> occ, tomb;  // bitmaps over edge slots: used (live or TOMB), TOMB
   uint64_t nbk = 0, ecap = 0, n_occ = 0, n_edges = 0, tn_cap = 0, fv_cap = 0;
   std::vector<uint32_t> fvbits;
@@ -354,6 +359,41 @@ struct TrieModel {
     if (fchild[0]) node_slot(fchild[0], sl);
     x.rh0 = sl[0];
     x.rh1 = sl[1];
+  }
+  // the walk's copy of the slot of the only literal child H of the root's half's '+' child
+  // (gm_kernels.h rp0/rp1), derived wherever root_half is, so it follows every change of H's slot
+  // in the same commit; rp0.z = NONE: none.  (H is at depth 3 under a '+' node: never fat, never
+  // a half; checked all the same.)
+  void root_plus_half(DevIndex& x) const {
+    uint4 sl[2] = {make_uint4(0u, 0u, NONE, 0u), make_uint4(0u, 0u, 0u, 0u)};
+    const uint32_t g = fchild[0], p = g ? pchild[g] : 0u;
+    if (p && nlit[p] == 1) {
+      const auto it = lone.find(p);
+      if (it != lone.end() && slot[it->second] != DEAD && parent[it->second] == p &&
+          !half[it->second] && !fchild[it->second])
+        node_slot(it->second, sl);
+    }
+    x.rp0 = sl[0];
+    x.rp1 = sl[1];
+  }
+  bool lone_parent(uint32_t par) const {  // a depth-2 '+' node
+    return par != 0 && tok[par] == PLUS_TOK && parent[par] != 0 && parent[parent[par]] == 0;
+  }
+  void lit_added(uint32_t par, uint32_t c) {  // after nlit[par] += 1 for the new child c
+    if (!lone_parent(par)) return;
+    if (nlit[par] == 1)
+      lone[par] = c;
+    else
+      lone.erase(par);
+  }
+  void lit_removed(uint32_t par) {  // a literal child of par went
+    if (lone_parent(par)) lone.erase(par);
+  }
+  void lone_rebuild() {  // from the node arrays (a snapshot load)
+    lone.clear();
+    for (uint32_t c = 1; c < parent.size(); ++c)
+      if (slot[c] != DEAD && tok[c] != PLUS_TOK && lone_parent(parent[c]) && nlit[parent[c]] == 1)
+        lone[parent[c]] = c;
   }
   // a filter was added along path[0] = root .. path[m] (its end node; hash_last: a '#' filter
   // hanging off path[m]): a code its ancestors can no longer guarantee is reset to unbounded
@@ -481,6 +521,8 @@ struct emqxgm {
   uint32_t pipe_wg_per_cu = 3;
   uint32_t leafp_mask = CF_HMASK;  // depth-code pruning (tune "leaf_prune")
   uint32_t psig_off = 0;           // 0x3F: the walk ignores lent signatures (tune "plus_sig" 0)
+  uint32_t rp_on = 1;              // the walk uses the root's '+' half (tune "root_plus_half")
+  uint32_t ks_on = 1;              // keyed siblings share a loaded line (tune "keyed_share")
   uint64_t census_depth[2 * CENSUS_DEPTHS] = {};  // the last census pass's loads per level
   uint8_t* d_in_bytes = nullptr;
   uint32_t* d_in_off = nullptr;
@@ -1156,6 +1198,7 @@ int upload_tables(emqxgm* h, const BuildIn& in, TrieModel& m, DevIndex& nx, Owne
   nx.root_pcf = root_p ? m.pcf(root_p) : 0u;
   nx.root_phf = root_p ? m.phf(root_p) : NONE;
   m.root_half(nx);
+  m.root_plus_half(nx);
   nx.test_mask = in.test_mask;
   nx.needs_verify = m.needs_verify;
   nx.full_mask = fmask;
@@ -1180,6 +1223,8 @@ void set_tables(DevIndex& to, const DevIndex& from) {
   x.fver = to.fver;
   x.leafp_mask = to.leafp_mask;
   x.psig_off = to.psig_off;
+  x.rp_on = to.rp_on;
+  x.ks_on = to.ks_on;
   to = x;
 }
 
@@ -1301,8 +1346,10 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
           *v = child;
           if (is_plus[w])
             m.pchild[cur] = child;
-          else
+          else {
             m.nlit[cur] += 1;
+            m.lit_added(cur, child);
+          }
         }
         cur = *v;
         m.ref[cur] += 1;
@@ -1631,8 +1678,10 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
       m.emap.erase(par, m.tok[n]);
       if (m.tok[n] == PLUS_TOK)
         m.pchild[par] = 0;
-      else
+      else {
         m.nlit[par] -= 1;
+        m.lit_removed(par);
+      }
       if (m.half[n]) {  // its slot is the parent's second half (or the root's arguments)
         m.fchild[par] = 0;
         m.half[n] = 0;
@@ -1713,6 +1762,7 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
           m.pchild[cur] = c;
         } else {
           m.nlit[cur] += 1;
+          m.lit_added(cur, c);
           m.sig[cur] |= (uint8_t)sig_bit(tok);
         }
         dirty.push_back(cur);
@@ -1817,6 +1867,7 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
   ix.root_pcf = root_p ? m.pcf(root_p) : 0u;
   ix.root_phf = root_p ? m.phf(root_p) : NONE;
   m.root_half(ix);
+  m.root_plus_half(ix);
   ix.needs_verify = m.needs_verify;
   ix.max_depth = m.max_depth;
   ix.fid_bound = (uint64_t)m.fv_cap * 32;
@@ -2425,6 +2476,8 @@ int pass_enqueue(emqxgm* h, PassCtx& c, const Epoch& E, const uint8_t* d_bytes,
   DevIndex ix = E.ix;
   ix.leafp_mask = h->leafp_mask;
   ix.psig_off = h->psig_off;
+  ix.rp_on = h->rp_on;
+  ix.ks_on = h->ks_on;
   // the epoch's uploads / patches must have landed (a full build's have: its wait is skipped)
   if (!E.ready_seen.load(std::memory_order_relaxed)) {
     if (hipEventQuery(E.ready) == hipSuccess)
@@ -3998,6 +4051,7 @@ int emqxgm_snapshot_load(emqxgm_t* h, const char* path) {
   // a resync generation belongs to the handle that ran it: a loaded handle's first resync must
   // not take the saved marks for its own (it would keep every key the table lost meanwhile)
   for (Filter& f : filters) f.sync_gen = 0;
+  m.lone_rebuild();
   {
     std::unique_lock<std::shared_mutex> pg(h->pmu);
     h->pool.swap(pool);
@@ -4877,6 +4931,18 @@ int emqxgm_tune(emqxgm_t* h, const char* key, int64_t value) {
     if (value < 0 || value > 1) return -EINVAL;
     std::lock_guard<std::mutex> g(h->mmu);
     h->psig_off = value ? 0u : 0x3Fu;
+    return 0;
+  }
+  if (strcmp(key, "root_plus_half") == 0) {  // 1 (default): the walk uses DevIndex::rp0/rp1
+    if (value < 0 || value > 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->rp_on = (uint32_t)value;
+    return 0;
+  }
+  if (strcmp(key, "keyed_share") == 0) {  // 1 (default): keyed siblings share a loaded line
+    if (value < 0 || value > 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->ks_on = (uint32_t)value;
     return 0;
   }
   if (strcmp(key, "spin_us") == 0) {  // host pipes' waits poll before they block

@@ -16,6 +16,9 @@ struct DevIndex {
   // the root's fat half (gm_common.h FAT_ID): its only literal child's slot, as a bucket's
   // second half would hold it (rh0.z = NONE: the root's literal children are probed by hash)
   uint4 rh0 = {0u, 0u, 0xFFFFFFFFu, 0u}, rh1 = {0u, 0u, 0u, 0u};
+  // the root's '+' half: when the half's '+' child has exactly one literal child H (cfg3:
+  // site/+ -> device), a copy of H's slot (H keeps its own in the table); rp0.z = NONE: none
+  uint4 rp0 = {0u, 0u, 0xFFFFFFFFu, 0u}, rp1 = {0u, 0u, 0u, 0u};
   const uint32_t* tn_of = nullptr;  // per node: non-wildcard trie keys ending there
   // publish fan-out tables (gm_fanout.inc), per filter id < fan_nf
   const uint4* fan = nullptr;        // [fan_nf] {rt off, rt count, dl off, dl count}
@@ -43,6 +46,8 @@ struct DevIndex {
   bool needs_verify = false;        // some trie filter has a hashed (long or test) token
   uint32_t leafp_mask = (1u << 26) | (1u << 29);  // CF_HMASK: depth-code pruning (0: off)
   uint32_t psig_off = 0;  // 0x3F: lent signatures (gm_common.h) are not used by the walk (A/B)
+  uint32_t rp_on = 1;     // 0: the walk ignores rp0/rp1 (tune "root_plus_half", A/B)
+  uint32_t ks_on = 1;     // 0: keyed siblings each take a probe (tune "keyed_share", A/B)
 };
 
 // Layout of the staged pairs of one pass.  Wide: {topic, filter, rank | REJ_BIT}, 12 B.  Packed

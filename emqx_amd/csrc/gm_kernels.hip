@@ -752,6 +752,10 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
   a.root_sig = ix.root_sig;
   a.rh0 = ix.rh0;
   a.rh1 = ix.rh1;
+  a.rp0 = ix.rp0;
+  a.rp1 = ix.rp1;
+  if (!ix.rp_on) a.rp0.z = NONE;
+  a.keyed_share = ix.ks_on;
   const dim3 grid(blocks);
   if (census) {
     if (level >= WALK_SPILL)

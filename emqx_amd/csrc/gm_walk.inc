@@ -73,6 +73,9 @@ struct WalkArgs {
                         // no claims (the atomics of a claim loop dominate small batches)
   uint32_t root_sig;    // the root's child signature
   uint4 rh0, rh1;       // the root's fat half (rh0.z low bits FAT_ID), or rh0.z = NONE
+  uint4 rp0, rp1;       // the slot of the only literal child of the half's '+' child (create RP),
+                        // or rp0.z = NONE (none, more than one, or tune "root_plus_half" 0)
+  uint32_t keyed_share; // 1: keyed siblings of a level share the loaded line (tune "keyed_share")
   unsigned long long* census;  // [0] states, [1] slot loads, [2] lane iters, [3] wave iters,
                                // then per wave {start, claims exhausted, end} (wall clock)
 };
@@ -282,7 +285,13 @@ __device__ __forceinline__ void visit(Lane& L, typename ItemT<CPT>::type (*s_stk
 // instruction count (small batches, indexes whose walks outgrow a lane's stack: cfg1, cfg2), lost
 // 1-2% to the filter's instructions in every form measured (MEASUREMENTS r07) and meets few
 // such probes; the one-lane-per-topic walks and the census have it.
-template <bool SPILL, uint32_t STK, bool CPT, bool FAT = false, bool LENT = true>
+// RP (the root's '+' half, with LENT in the same walks): 1 = the root's state, which hands 2 to
+// its fat half G's.  G's carried '+' child p then takes no literal item when p's literal children
+// are one node H alone and the arguments carry H's slot (A.rp0/rp1, a copy: H keeps its slot in
+// the table, and "absent" is always right): word d+1 against H's token decides here what the
+// probe (p, word d+1) would have found a round trip later -- the same hot line for every topic
+// of a batch (cfg3: site/+ -> device).  H's state is created exactly as a resolved probe's.
+template <bool SPILL, uint32_t STK, bool CPT, bool FAT = false, bool LENT = true, uint32_t RP = 0>
 __device__ __forceinline__ void create(Lane& L, typename ItemT<CPT>::type (*s_stk)[WG], uint32_t (*s_em)[WG],
                                        const uint64_t (*s_tw)[WG], const WalkArgs& A,
                                        uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig,
@@ -316,16 +325,30 @@ __device__ __forceinline__ void create(Lane& L, typename ItemT<CPT>::type (*s_st
   visit<SPILL, STK, CPT>(L, s_stk, s_em, A, cf, hf, tw, d, lit, keyed ? IT_KEYED : 0u);
   states += 1;
   if (FAT && fat_go)
-    create<SPILL, STK, CPT, false, LENT>(L, s_stk, s_em, s_tw, A, h0.w, h1.x, h1.y, h0.z >> SIG_SHIFT,
-                                         h1.z, h1.w, d + 1, true, true, states);
+    create<SPILL, STK, CPT, false, LENT, (RP == 1 ? 2u : 0u)>(L, s_stk, s_em, s_tw, A, h0.w, h1.x, h1.y,
+                                                             h0.z >> SIG_SHIFT, h1.z, h1.w, d + 1,
+                                                             true, true, states);
   if (!plus_ok || d >= L.n || !(cf & CF_PLUS)) return;
   const bool ptw = (pcf & CF_PTW) != 0;
   if (d + 1 == L.n && (pcf & CF_TW) && !ptw) {
     push_item<SPILL, STK, CPT>(L, s_stk, A, IT_PLUS | (cf & CF_ID_MASK), d);
     return;
   }
+  // (RP: the copy is p's child -- its parent word says so -- and p would take a literal item)
+  bool rp = false;
+  if constexpr (RP == 2) {
+    rp = (A.rp0.z & CF_ID_MASK) == (pcf & CF_ID_MASK) && (pcf & CF_LIT) && d + 1 < L.n;
+    pcf = rp ? (pcf & ~CF_LIT) : pcf;
+  }
   visit<SPILL, STK, CPT>(L, s_stk, s_em, A, pcf & ~CF_PTW, ptw ? NONE : phf, ptw ? phf : NONE, d + 1, false);
   states += 1;
+  if constexpr (RP == 2) {
+    const uint64_t ptok = s_tw[d + 1 < REC_TOKS ? d + 1 : REC_TOKS - 1][L.tcol];
+    if (rp && (uint32_t)ptok == A.rp0.x && (uint32_t)(ptok >> 32) == A.rp0.y)
+      create<SPILL, STK, CPT, false, LENT>(L, s_stk, s_em, s_tw, A, A.rp0.w, A.rp1.x, A.rp1.y,
+                                           A.rp0.z >> SIG_SHIFT, A.rp1.z, A.rp1.w, d + 2, true, true,
+                                           states);
+  }
   if (d + 1 < L.n && (pcf & CF_PLUS))
     push_item<SPILL, STK, CPT>(L, s_stk, A, IT_PLUS | (pcf & CF_ID_MASK), d + 1);
 }
@@ -359,11 +382,27 @@ __device__ __forceinline__ uint32_t pair_xchg(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
 }
 
+
+// SHARE (r09; the compact one-lane-per-topic walks).  An IT_KEYED item's home bucket is a hash of
+// its level's token alone (gm_common.h edge_home), so the keyed items of one topic at one level
+// probe the same line (cfg3: site/+/device -> D and site/S/device -> D).  When slot 0 is filled
+// with a keyed probe at its home, a keyed item of the same level on top of the stack is not given
+// a slot of its own: it stays there, and after the resolves the first such item on the stack from
+// that point up -- those pushed by this iteration's resolves included -- is decided from slot 0's
+// line, still in its registers: found -> its child state is created now; the bucket has an empty
+// slot -> no such child; a full bucket of other keys -> the item stays and is probed the ordinary
+// way from its home.  One item per lane and iteration (a loop over all of them, with its flush,
+// cost the cfg3 kernel a wave per SIMD: MEASUREMENTS r09); a further sibling takes its own probe.
+// Only slot 0 anchors a shared line: its fields are read at a constant index (a select between
+// two P[] fields puts the array into scratch).  A slot that has moved along a chain is not at an
+// item's home and shares nothing.
 template <bool CENSUS, bool SPILL, uint32_t STK, bool CPT = false, bool PAIR = false>
 __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
   static_assert(!(CPT && SPILL), "compact items live in LDS only");
   static_assert(!PAIR || (CPT && !SPILL && !CENSUS), "pairs: the compact LDS-only production walk");
   constexpr uint32_t NS = PAIR ? PAIR_WSLOTS : WSLOTS;  // probe slots per lane
+  constexpr bool SHARE = CPT && !PAIR;
+  constexpr uint32_t RP = PAIR ? 0u : 1u;  // (the pair walk: compiled out, as LENT is)
   __shared__ typename ItemT<CPT>::type s_stk[STK][WG];
   __shared__ uint32_t s_em[EMX][WG];
   __shared__ uint64_t s_tw[REC_TOKS][WG];  // the lane's topic's level tokens 0..6
@@ -458,7 +497,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         // the root: no root '#' and no root '+' for a '$' topic (emqx_trie.erl:282-289); a
         // pair's root state is its leading lane's (the partner takes items from it)
         if (lead)
-          create<SPILL, STK, CPT, true, !PAIR>(L, s_stk, s_em, s_tw, A, A.root_cf, dollar ? NONE : A.root_hf, NONE,
+          create<SPILL, STK, CPT, true, !PAIR, RP>(L, s_stk, s_em, s_tw, A, A.root_cf, dollar ? NONE : A.root_hf, NONE,
                         A.root_sig, A.root_pcf,
                         A.root_phf, 0, !dollar, false, c_states,
                         (A.rh0.z & CF_ID_MASK) == FAT_ID, A.rh0, A.rh1);
@@ -550,9 +589,19 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
       L.sp -= own + min(pfr - pown, L.sp - own);  // (and what the partner takes from mine)
       __builtin_amdgcn_wave_barrier();  // the partner's pushes of the last iteration are in LDS
     }
+    // SHARE: the level of slot 0's keyed probe when it is filled here, at its home (else NONE),
+    // and the stack position from which the items are matched against its line after the resolves
+    uint32_t shk = NONE, sh_lo = 0;
 #pragma unroll
     for (uint32_t j = 0; j < NS; ++j) {
       Probe& p = P[j];
+      if constexpr (SHARE) {
+        // a keyed sibling of slot 0's probe stays on the stack (and so does everything below it)
+        if (j > 0 && active && !p.busy && own_left > 0 && shk != NONE) {
+          const uint32_t v = s_stk[own_pos - 1][L.tid];
+          if ((v & IT_KIND) == IT_KEYED && ((v >> CPT_SHIFT) & 0xFu) == shk) own_left = 0;
+        }
+      }
       if (active && !p.busy && (own_left > 0 || st_left > 0)) {
         uint32_t pos, col = L.tid;
         if (own_left > 0) {
@@ -568,6 +617,8 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         if constexpr (CPT) {
           const uint32_t v = s_stk[pos][col];
           it = make_uint2(v & ~(0xFu << CPT_SHIFT), (v >> CPT_SHIFT) & 0xFu);
+          if constexpr (SHARE)
+            if (j == 0) shk = (A.keyed_share && (v & IT_KIND) == IT_KEYED && it.y < REC_TOKS) ? it.y : NONE;
         } else if (!SPILL || L.sp < STK) {
           it = s_stk[L.sp][L.tid];
         } else {
@@ -592,6 +643,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         if (!p.side) p.ia = edge_home(it.x & CF_ID_MASK, p.key, A.emask, kind == IT_KEYED);
       }
     }
+    if constexpr (SHARE) sh_lo = (shk != NONE && L.sp > 0) ? L.sp - 1 : L.sp;
     // ---- one memory round trip: every slot issues its load, branch-free (an idle slot loads
     // slot 0, an always-cached line, and ignores it): with the loads of all slots in one basic
     // block the compiler keeps them in flight together instead of draining vmcnt between ----
@@ -709,7 +761,9 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
     // state ('#' filter, carried '+' child's '#' filter) and, per slot, a resolved child
     // ('#' filter, terminal filters, carried '+' child's '#' filter) or one tn list.
     // A state that brings its fat half lists up to 2 + 3 ids (its own '#' filter and carried
-    // '+' child's, then the half's three), the new topic's root with the root's half as many:
+    // '+' child's, then the half's three), the new topic's root with the root's half as many --
+    // and, when the half's '+' child's only child comes from the arguments (create RP: topics of
+    // 3 and more levels, so the half lists no terminal filters), 2 + 2 + 3 from an empty list:
     // before a slot is resolved the wave flushes if some lane could pass EMX.
     static_assert(EMX >= 5 + 3, "a flush must hold a slot's emissions after a partial list");
 #pragma unroll
@@ -750,6 +804,47 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         p.busy = false;
       } else {
         p.ia = (p.ia + 1) & A.emask;
+      }
+    }
+
+    // ---- SHARE: the keyed items of slot 0's level against slot 0's line ----
+    if constexpr (SHARE) {
+      // (one item per lane: the first found; a create lists up to 5 ids, so the flush check
+      // comes first.  A second sibling, rare, is probed the ordinary way.)
+      uint32_t node = NONE, fi = 0;
+      if (shk != NONE) {
+        for (uint32_t i = sh_lo; i < L.sp; ++i) {
+          const uint32_t v = s_stk[i][L.tid];
+          if ((v & IT_KIND) == IT_KEYED && ((v >> CPT_SHIFT) & 0xFu) == shk) {
+            node = v & CF_ID_MASK;
+            fi = i;
+            break;
+          }
+        }
+      }
+      if (__ballot(node != NONE) != 0) {
+        if (__ballot(L.ne + 5u > EMX) != 0) flush();
+        if (node != NONE) {
+          const uint4 a0 = P[0].s0, a1 = P[0].s1, b0 = P[0].t0, b1 = P[0].t1;
+          const uint32_t klo = (uint32_t)P[0].key, khi = (uint32_t)(P[0].key >> 32);
+          const bool ha = (a0.z & CF_ID_MASK) == node && a0.x == klo && a0.y == khi;
+          const bool hb = (b0.z & CF_ID_MASK) == node && b0.x == klo && b0.y == khi;
+          if (ha || hb || a0.z == NONE || b0.z == NONE) {
+            // decided by this line: the item leaves the stack (the top one takes its place)
+            --L.sp;
+            s_stk[fi][L.tid] = s_stk[L.sp][L.tid];
+          }
+          // (else a full bucket of other keys: the item stays, for a probe of its own)
+          if (ha || hb) {
+            const uint32_t ccf = ha ? a0.w : b0.w, chf = ha ? a1.x : b1.x;
+            const uint32_t ctw = ha ? a1.y : b1.y, cpcf = ha ? a1.z : b1.z;
+            const uint32_t cphf = ha ? a1.w : b1.w;
+            const uint32_t csig = (ha ? a0.z : b0.z) >> SIG_SHIFT;
+            const bool fat = ha && (b0.z & CF_ID_MASK) == FAT_ID;
+            create<SPILL, STK, CPT, true, !PAIR>(L, s_stk, s_em, s_tw, A, ccf, chf, ctw, csig, cpcf, cphf,
+                                                 shk + 1, true, true, c_states, fat, b0, b1);
+          }
+        }
       }
     }
 

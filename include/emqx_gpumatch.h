@@ -676,7 +676,15 @@ int emqxgm_set_profiling(emqxgm_t* h, int on);
  * is built without this filter: it runs batches of at most half the walk grid's
  * lanes, every batch of an index whose walks outgrew a lane's shallow stack, and every batch at
  * "walk_pair" 2; emqxgm_walk_census always runs a one-lane walk with the filter, so for such
- * passes it counts slightly fewer loads than the production kernel issues); "host_out" (host pipes copy results to the
+ * passes it counts slightly fewer loads than the production kernel issues);
+ * "root_plus_half" (1 default: when the root's only literal child G rides in the walk's arguments
+ * and G's '+' child has exactly one literal child H, a copy of H's slot rides there too and the walk
+ * decides (G/+, word 2) from it without a probe; 0: the copy is ignored) and "keyed_share"
+ * (1 default: the keyed items of one topic at one level, which share a home bucket, are decided
+ * from one loaded line; 0: each takes a probe of its own) -- both A/B switches from the next pass
+ * on, no rebuild, same rows either way (a row's order may differ); like "plus_sig" they act in the
+ * one-lane-per-topic walks and the census, and the pair walk is built without them;
+ * "host_out" (host pipes copy results to the
  * host with hipMemcpyAsync, 0 default, or with a kernel writing host memory, 1);
  * "walk_pair" (1 default: a batch of at most half the walk grid's lanes is walked by two lanes
  * per topic; 0: one lane per topic); "exact_range_kb" (0 default: one route-key probe pass over the whole table; > 0: the probe
