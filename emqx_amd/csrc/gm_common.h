@@ -91,7 +91,8 @@ GM_HD uint64_t key_hash(const uint8_t* p, uint32_t len, uint64_t mask) {
 // Slots come in 64-B buckets of EBUCKET (one line: a probe loads and checks both slots, so a
 // collision inside the bucket costs no extra round trip); an edge goes to the first free slot
 // of its home bucket (edge_slot) or of the buckets after it, and a lookup stops at a bucket
-// with a free slot.
+// with a free slot -- or at a closed one (EDGE_CLOSED below: s1.w of a slot whose child has no
+// '+' child, where p.hf has no reader).
 constexpr uint32_t SLOT_U4 = 2;
 constexpr uint32_t EBUCKET = 2;
 constexpr uint32_t EDGE_SLACK = 4;  // slots >= 4 x edges (load <= 1/4): fewer bucket overflows
@@ -122,6 +123,19 @@ constexpr uint32_t FAT_MAX_DEPTH = 6;  // C's word (level depth(C)) is a record 
 // is C's own (0: keyed, below).  The same rule holds for a fat half's word (FAT_ID | field), the
 // root's half in the kernel arguments and the root's own signature.  A reader that ignores lent
 // bits is still exact: they only ever drop probes that find nothing.
+// Closed buckets (r10).  A bucket is closed when no live edge whose chain (the buckets from its
+// home to its slot) starts at or passes through it sits beyond it: a lookup that finds neither
+// its key nor an empty slot there ends with "no such child" instead of loading the next bucket.
+// The mark lives in the bucket's own line: s1.w of a live slot whose child has no '+' child
+// (CF_PLUS clear in its cf, so no reader looks at the carried p.hf) holds EDGE_CLOSED instead of
+// NONE while its bucket is closed.  Every such slot of the bucket carries it, the halves of a fat
+// bucket included; a bucket whose children all have a '+' child goes unmarked, and so do empty
+// slots, TOMB slots and the copies in the kernel arguments.  A reader tests CF_PLUS first (the
+// value alone could be a p.hf).  Marks are taken away in the commit that places an edge past
+// the bucket and come back only with a full build or a snapshot load, which derive them from the
+// placement (tune "closed_buckets" 0: the walk ignores them).  A reader that ignores the mark is
+// still exact: it only ever ends chains that find nothing.
+constexpr uint32_t EDGE_CLOSED = 0xFFFFFFFCu;
 constexpr uint32_t SIG_SHIFT = CF_ID_BITS;
 constexpr uint32_t SIG_CLASSES = 6;
 GM_HD uint32_t sig_class(uint64_t tok) {
@@ -150,6 +164,11 @@ constexpr uint32_t CF_TN = 1u << 31;    // child terminates >=1 non-wildcard tri
 // emits them without a '+' probe.
 constexpr uint32_t CF_PTW = 1u << 31;
 constexpr uint32_t LIST_MULTI = 0x80000000u;  // tw/tn value is a multi[] index
+// The closed mark of a slot {.., cf}, {.., .., .., phf} (EDGE_CLOSED above); `off` = 0, or 1 when
+// marks are ignored (bit 0 of EDGE_CLOSED is clear, so the comparison then never holds).
+GM_HD bool slot_closed(uint32_t cf, uint32_t phf, uint32_t off) {
+  return !(cf & CF_PLUS) && (phf | off) == EDGE_CLOSED;
+}
 
 GM_HD uint64_t edge_slot(uint32_t parent, uint64_t tok, uint64_t mask) {
   return fmix64(tok ^ ((uint64_t)parent * 0x9e3779b97f4a7c15ull)) & mask;

@@ -275,6 +275,13 @@ struct TrieModel {
   // is always correct).  Feeds root_plus_half; not part of a snapshot (lone_rebuild).
   std::unordered_map<uint32_t, uint32_t> lone;
   std::vector<uint64_t> occ, tomb;  // bitmaps over edge slots: used (live or TOMB), TOMB
+  // closed buckets (gm_common.h EDGE_CLOSED).  open: a bit per bucket, set when some edge whose
+  // chain passes the bucket was placed beyond it -- exact after a full build and a snapshot load
+  // (closed_rebuild), only ever set by delta commits (a deletion leaves it).  owner: the node of
+  // each slot's live edge (NONE: empty or TOMB), so that a delta commit that opens a bucket can
+  // re-emit the slots that carried its mark.  Neither is part of a snapshot.
+  std::vector<uint64_t> open;
+  std::vector<uint32_t> owner;
   uint64_t nbk = 0, ecap = 0, n_occ = 0, n_edges = 0, tn_cap = 0, fv_cap = 0;
   std::vector<uint32_t> fvbits;
   std::vector<uint32_t> multi;  // [count, fid...] lists of nodes shared by several filters
@@ -323,7 +330,33 @@ struct TrieModel {
     const uint32_t p = pchild[c];
     sl[0] = make_uint4((uint32_t)tok[c], (uint32_t)(tok[c] >> 32),
                        (half[c] ? FAT_ID : parent[c]) | (sig_field(c) << SIG_SHIFT), cf(c));
-    sl[1] = make_uint4(hfd(c), tw[c], p ? pcf(p) : 0u, p ? phf(p) : NONE);
+    sl[1] = make_uint4(hfd(c), tw[c], p ? pcf(p) : 0u, p ? phf(p) : closed_mark(c));
+  }
+  // s1.w of a slot whose node has no '+' child: EDGE_CLOSED while its bucket is closed (the
+  // root's half, carried in the arguments, has no bucket)
+  uint32_t closed_mark(uint32_t c) const {
+    const uint64_t s = slot[c];
+    if (s == DEAD || s == ROOTH || (s / EBUCKET >> 6) >= open.size()) return NONE;
+    return (open[s / EBUCKET >> 6] >> (s / EBUCKET & 63)) & 1 ? NONE : EDGE_CLOSED;
+  }
+  // open and owner from the placement: every bucket from an edge's home up to its slot's is
+  // open (a fat half sits in its parent's bucket, on no chain of its own).  False: some slot is
+  // not on its edge's chain (a corrupt snapshot).
+  bool closed_rebuild() {
+    open.assign(nbk / 64 + 1, 0ull);
+    owner.assign(ecap, NONE);
+    for (uint32_t c = 1; c < parent.size(); ++c) {
+      if (slot[c] == DEAD || slot[c] == ROOTH) continue;
+      if (slot[c] >= ecap || owner[slot[c]] != NONE) return false;
+      owner[slot[c]] = c;
+      if (half[c]) continue;
+      uint64_t b = home(parent[c], tok[c]), steps = 0;
+      for (; b != slot[c] / EBUCKET; b = (b + 1) & (nbk - 1)) {
+        if (++steps >= nbk) return false;
+        open[b >> 6] |= 1ull << (b & 63);
+      }
+    }
+    return true;
   }
   // the carried copy of '+' child p (gm_common.h CF_PTW): its '#' filter, or -- when it has
   // none -- its terminal filters, flagged
@@ -523,6 +556,7 @@ struct emqxgm {
   uint32_t psig_off = 0;           // 0x3F: the walk ignores lent signatures (tune "plus_sig" 0)
   uint32_t rp_on = 1;              // the walk uses the root's '+' half (tune "root_plus_half")
   uint32_t ks_on = 1;              // keyed siblings share a loaded line (tune "keyed_share")
+  uint32_t cb_on = 1;              // lookups end at closed buckets (tune "closed_buckets")
   uint64_t census_depth[2 * CENSUS_DEPTHS] = {};  // the last census pass's loads per level
   uint8_t* d_in_bytes = nullptr;
   uint32_t* d_in_off = nullptr;
@@ -1225,6 +1259,7 @@ void set_tables(DevIndex& to, const DevIndex& from) {
   x.psig_off = to.psig_off;
   x.rp_on = to.rp_on;
   x.ks_on = to.ks_on;
+  x.cb_on = to.cb_on;
   to = x;
 }
 
@@ -1460,6 +1495,7 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
     }
   m.n_occ = 0;
   for (uint64_t w : m.occ) m.n_occ += (uint64_t)__builtin_popcountll(w);
+  if (!m.closed_rebuild()) return fail(h, hipErrorUnknown, "edge placement: a slot off its chain");
   // node side array with headroom for delta-commit growth
   m.tn_cap = n_nodes + std::max<uint64_t>(4096, n_nodes / 4);
   m.n_nodes0 = n_nodes;
@@ -1689,6 +1725,7 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
       if (m.slot[n] != ROOTH) {
         bset(m.tomb, m.slot[n]);
         epatch[m.slot[n]] = NONE;
+        m.owner[m.slot[n]] = NONE;
       }
       m.slot[n] = DEAD;
       m.n_edges -= 1;
@@ -1698,6 +1735,9 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
   }
 
   // ---- trie inserts: new nodes take the first free or TOMB slot of their bucket chain ----
+  // (a bucket the new edge passes is no longer closed, gm_common.h EDGE_CLOSED: the slots that
+  // carried its mark are re-emitted with this commit's patches, below)
+  std::vector<uint64_t> opened;
   auto alloc_slot = [&](uint32_t par, uint64_t tok) {
     uint64_t b = m.home(par, tok), i = DEAD;
     while (i == DEAD) {
@@ -1711,6 +1751,10 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
           bclr(m.tomb, q);
           i = q;
         }
+      }
+      if (i == DEAD && !bit(m.open, b)) {
+        bset(m.open, b);
+        opened.push_back(b);
       }
       b = (b + 1) & (m.nbk - 1);
     }
@@ -1745,10 +1789,12 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
           if (m.slot[fc] != ROOTH) {
             bset(m.tomb, m.slot[fc]);
             epatch[m.slot[fc]] = NONE;
+            m.owner[m.slot[fc]] = NONE;
           }
           m.half[fc] = 0;
           m.fchild[cur] = 0;
           m.slot[fc] = alloc_slot(cur, m.tok[fc]);
+          m.owner[m.slot[fc]] = fc;
           epatch[m.slot[fc]] = fc;
           dirty.push_back(fc);
         }
@@ -1756,6 +1802,7 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
         *v = c;
         const uint64_t i = alloc_slot(cur, tok);
         m.slot[c] = i;
+        m.owner[i] = c;
         epatch[i] = c;
         m.n_edges += 1;
         if (is_plus[w]) {
@@ -1837,6 +1884,9 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
     if (par != NONE && par != 0 && m.pchild[par] == n && m.slot[par] != ROOTH)
       epatch[m.slot[par]] = par;
   }
+  for (uint64_t b : opened)
+    for (uint32_t j = 0; j < EBUCKET; ++j)
+      if (m.owner[b * EBUCKET + j] != NONE) epatch[b * EBUCKET + j] = m.owner[b * EBUCKET + j];
   // ---- stage the patches, upload them in one copy, apply them in one launch ----
   if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, hipErrorInvalidDevice, "hipSetDevice");
   PatchList& pl = h->patches;
@@ -2478,6 +2528,7 @@ int pass_enqueue(emqxgm* h, PassCtx& c, const Epoch& E, const uint8_t* d_bytes,
   ix.psig_off = h->psig_off;
   ix.rp_on = h->rp_on;
   ix.ks_on = h->ks_on;
+  ix.cb_on = h->cb_on;
   // the epoch's uploads / patches must have landed (a full build's have: its wait is skipped)
   if (!E.ready_seen.load(std::memory_order_relaxed)) {
     if (hipEventQuery(E.ready) == hipSuccess)
@@ -4052,6 +4103,12 @@ int emqxgm_snapshot_load(emqxgm_t* h, const char* path) {
   // not take the saved marks for its own (it would keep every key the table lost meanwhile)
   for (Filter& f : filters) f.sync_gen = 0;
   m.lone_rebuild();
+  // the closed-bucket bits and the slot owners are derived, like `lone`: an edge that is not on
+  // its own chain (a lookup would never find it) or two edges in one slot fail the load
+  if (!m.closed_rebuild()) {
+    set_err(h, "snapshot corrupt: edge chain");
+    return -EINVAL;
+  }
   {
     std::unique_lock<std::shared_mutex> pg(h->pmu);
     h->pool.swap(pool);
@@ -4943,6 +5000,12 @@ int emqxgm_tune(emqxgm_t* h, const char* key, int64_t value) {
     if (value < 0 || value > 1) return -EINVAL;
     std::lock_guard<std::mutex> g(h->mmu);
     h->ks_on = (uint32_t)value;
+    return 0;
+  }
+  if (strcmp(key, "closed_buckets") == 0) {  // 1 (default): lookups end at closed buckets
+    if (value < 0 || value > 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->cb_on = (uint32_t)value;
     return 0;
   }
   if (strcmp(key, "spin_us") == 0) {  // host pipes' waits poll before they block

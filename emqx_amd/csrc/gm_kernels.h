@@ -48,6 +48,7 @@ struct DevIndex {
   uint32_t psig_off = 0;  // 0x3F: lent signatures (gm_common.h) are not used by the walk (A/B)
   uint32_t rp_on = 1;     // 0: the walk ignores rp0/rp1 (tune "root_plus_half", A/B)
   uint32_t ks_on = 1;     // 0: keyed siblings each take a probe (tune "keyed_share", A/B)
+  uint32_t cb_on = 1;     // 0: the walk ignores closed-bucket marks (tune "closed_buckets", A/B)
 };
 
 // Layout of the staged pairs of one pass.  Wide: {topic, filter, rank | REJ_BIT}, 12 B.  Packed

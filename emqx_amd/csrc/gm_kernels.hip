@@ -756,6 +756,7 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
   a.rp1 = ix.rp1;
   if (!ix.rp_on) a.rp0.z = NONE;
   a.keyed_share = ix.ks_on;
+  a.closed_off = ix.cb_on ? 0u : 1u;
   const dim3 grid(blocks);
   if (census) {
     if (level >= WALK_SPILL)

@@ -26,6 +26,9 @@
 
 constexpr uint32_t WSLOTS = 2;             // probes in flight per lane per iteration
 constexpr uint32_t PAIR_WSLOTS = 2;        // ... per lane of a pair walk (r05: 1 and 3 slower)
+// the pair walk ends lookups at closed buckets too (r10: compiled out like LENT / RP / SHARE --
+// the pair walk is bound by its instruction count and was not measured with the rule)
+constexpr bool WALK_CLOSED_PAIR = false;
 // probe items per lane kept in LDS: STK (a k_walk template parameter) = WALK_STK_SHALLOW or
 // WALK_STK_DEEP (gm_kernels.h); the spilling variant continues in global memory
 constexpr uint32_t EMX = 8;                // emissions per lane per flush (<= 2 + 3 + 3, below)
@@ -76,6 +79,8 @@ struct WalkArgs {
   uint4 rp0, rp1;       // the slot of the only literal child of the half's '+' child (create RP),
                         // or rp0.z = NONE (none, more than one, or tune "root_plus_half" 0)
   uint32_t keyed_share; // 1: keyed siblings of a level share the loaded line (tune "keyed_share")
+  uint32_t closed_off;  // 0, or 1: closed-bucket marks are ignored (tune "closed_buckets" 0;
+                        // gm_common.h slot_closed)
   unsigned long long* census;  // [0] states, [1] slot loads, [2] lane iters, [3] wave iters,
                                // then per wave {start, claims exhausted, end} (wall clock)
 };
@@ -403,6 +408,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
   constexpr uint32_t NS = PAIR ? PAIR_WSLOTS : WSLOTS;  // probe slots per lane
   constexpr bool SHARE = CPT && !PAIR;
   constexpr uint32_t RP = PAIR ? 0u : 1u;  // (the pair walk: compiled out, as LENT is)
+  constexpr bool CLOSED = WALK_CLOSED_PAIR || !PAIR;  // closed buckets (gm_common.h EDGE_CLOSED)
   __shared__ typename ItemT<CPT>::type s_stk[STK][WG];
   __shared__ uint32_t s_em[EMX][WG];
   __shared__ uint64_t s_tw[REC_TOKS][WG];  // the lane's topic's level tokens 0..6
@@ -800,7 +806,9 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         const bool fat = ha && (b0.z & CF_ID_MASK) == FAT_ID;
         create<SPILL, STK, CPT, true, !PAIR>(L, s_stk, s_em, s_tw, A, ccf, chf, ctw, csig, cpcf, cphf, p.k + 1,
                                  true, (p.cur & IT_KIND) != IT_PLUS, c_states, fat, b0, b1);
-      } else if (a0.z == NONE || b0.z == NONE) {
+      } else if (a0.z == NONE || b0.z == NONE ||
+                 (CLOSED && (slot_closed(a0.w, a1.w, A.closed_off) || slot_closed(b0.w, b1.w, A.closed_off)))) {
+        // (a closed bucket, gm_common.h EDGE_CLOSED: nothing on this chain was placed past it)
         p.busy = false;
       } else {
         p.ia = (p.ia + 1) & A.emask;
@@ -829,12 +837,15 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
           const uint32_t klo = (uint32_t)P[0].key, khi = (uint32_t)(P[0].key >> 32);
           const bool ha = (a0.z & CF_ID_MASK) == node && a0.x == klo && a0.y == khi;
           const bool hb = (b0.z & CF_ID_MASK) == node && b0.x == klo && b0.y == khi;
-          if (ha || hb || a0.z == NONE || b0.z == NONE) {
-            // decided by this line: the item leaves the stack (the top one takes its place)
+          if (ha || hb || a0.z == NONE || b0.z == NONE ||
+              (CLOSED && (slot_closed(a0.w, a1.w, A.closed_off) || slot_closed(b0.w, b1.w, A.closed_off)))) {
+            // decided by this line (a closed bucket of other keys: the sibling is absent as
+            // well): the item leaves the stack (the top one takes its place)
             --L.sp;
             s_stk[fi][L.tid] = s_stk[L.sp][L.tid];
           }
-          // (else a full bucket of other keys: the item stays, for a probe of its own)
+          // (else a full bucket of other keys with an edge placed past it: the item stays, for
+          // a probe of its own)
           if (ha || hb) {
             const uint32_t ccf = ha ? a0.w : b0.w, chf = ha ? a1.x : b1.x;
             const uint32_t ctw = ha ? a1.y : b1.y, cpcf = ha ? a1.z : b1.z;

@@ -684,6 +684,10 @@ int emqxgm_set_profiling(emqxgm_t* h, int on);
  * from one loaded line; 0: each takes a probe of its own) -- both A/B switches from the next pass
  * on, no rebuild, same rows either way (a row's order may differ); like "plus_sig" they act in the
  * one-lane-per-topic walks and the census, and the pair walk is built without them;
+ * "closed_buckets" (1 default: a lookup that finds neither its edge nor an empty slot in a bucket
+ * ends there when the bucket's line says that no edge was placed past it; 0: the marks
+ * are ignored and every such lookup goes on to the next bucket -- an A/B switch like the two above,
+ * from the next pass on, same rows; the pair walk is built without the rule);
  * "host_out" (host pipes copy results to the
  * host with hipMemcpyAsync, 0 default, or with a kernel writing host memory, 1);
  * "walk_pair" (1 default: a batch of at most half the walk grid's lanes is walked by two lanes
