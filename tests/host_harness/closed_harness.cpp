@@ -1,7 +1,9 @@
 // closed_harness.cpp -- TEST INFRASTRUCTURE: closed edge buckets (gm_common.h EDGE_CLOSED), on the CPU.
 //
-// Built by tests/test_closed_host.py with g++ -fsanitize=address,undefined against the fake HIP
-// runtime of this directory, like rph_harness.cpp, and run directly.  A cfg3 miniature and a random
+// Built by tests/test_closed_host.py (tests/host_build.py) under ASan + UBSan against the fake HIP
+// runtime of this directory, like rph_harness.cpp, and run directly; the rig is harness_rig.h's, the
+// restated walk harness_walk.h's SlotWalk, run with the switch cb off and on and with lent, rp
+// and ks as the committed index has them (all on).  A cfg3 miniature and a random
 // cfg2-like trie are built -- plain and with 3-bit collision tokens, keyed on / auto, fat buckets
 // on / off -- and churned by delta commits: inserts whose home bucket is full and closed (the
 // word is chosen by its edge_home), deletes, re-inserts into the TOMB slots, a fat half moving
@@ -12,8 +14,8 @@
 //   * no bucket on a live edge's chain before its slot carries a mark or a closed bit;
 //   * a mark sits only on a live slot whose node has no '+' child, in a bucket the model has
 //     closed; the copies in the arguments carry none that a reader could take for one;
-//   * the rows of the unchanged reader (harness_walk.h), of a restatement of k_walk's iteration
-//     with the rule on and off, and of the oracle are equal.
+//   * the rows of the plain reader (harness_walk.h CpuWalk), of the restatement of k_walk's
+//     iteration with the rule on and off, and of the oracle are equal.
 // Prints "OK <commits> <delta commits> <buckets opened by a delta> <inserts past a closed full
 // bucket> <lookups stopped at a closed bucket> <row checks>".
 #include <unistd.h>
@@ -21,277 +23,32 @@
 #include <atomic>
 #include <thread>
 
-#include "harness_walk.h"
+#include "harness_rig.h"
 
 namespace {
 
-uint64_t g_commits = 0, g_deltas = 0, g_opened = 0, g_past = 0, g_stops = 0, g_rows = 0, g_marks = 0;
+uint64_t g_opened = 0, g_past = 0, g_stops = 0, g_marks = 0;
 uint64_t g_loads[2] = {0, 0}, g_iters[2] = {0, 0};
 
-// k_walk's iteration restated (gm_walk.inc, NS = 2 slots; lent signatures, SHARE and RP as the
-// compact one-lane-per-topic walks and the census have them), with the closed-bucket rule behind
-// `cb_on`.
-struct SlotWalk {
-  const DevIndex& ix;
-  const bool cb_on;
-  std::vector<uint64_t> toks;
-  uint32_t n = 0;
-  bool dollar = false;
-  std::vector<uint32_t> out;
-  std::vector<std::pair<uint32_t, uint32_t>> stk;  // (node | item kind, level)
-  uint64_t loads = 0, iters = 0, stops = 0;
-  bool walked = false;  // the topic reached the walk (not a wildcard name, the trie not empty)
-  static constexpr uint32_t IT_PLUS = 0x80000000u, IT_TN = 0x40000000u;
-  static constexpr uint32_t IT_KEYED = IT_PLUS | IT_TN, IT_KIND = IT_PLUS | IT_TN;
-  struct Slot {
-    bool busy = false, side = false;
-    uint32_t cur = 0, k = 0;
-    uint64_t key = 0, ia = 0;
-  };
+// The restated walk as production runs it on the rig's handle -- lent signatures on, "root_plus_half"
+// and "keyed_share" as the committed index has them (1) -- with tune "closed_buckets" 0 / 1.
+WalkRules closed_rules(const DevIndex& ix, bool on) {
+  WalkRules rules(ix);
+  rules.cb = on;
+  return rules;
+}
 
-  SlotWalk(const DevIndex& x, bool cb) : ix(x), cb_on(cb) {}
-  void em(uint32_t v) {
-    if (v == NONE) return;
-    if (v & LIST_MULTI) {
-      const uint32_t i = v & ~LIST_MULTI, c = ix.multi[i];
-      for (uint32_t j = 0; j < c; ++j) out.push_back(ix.multi[i + 1 + j]);
-    } else {
-      out.push_back(v);
-    }
-  }
-  uint32_t strip(uint32_t cf, uint32_t d) const {
-    const uint32_t h = cf_depth_code(cf & ix.leafp_mask);
-    return (h != 0u && (int)(n - d) > (int)h) ? (cf & ~(CF_LIT | CF_PLUS)) : cf;
-  }
-  void visit(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t d, bool lit, uint32_t kind = 0) {
-    if (hf != NONE) em(hf);
-    if (d == n) {
-      if (cf & CF_TW) em(tw);
-      if (lit && (cf & CF_TN) && dollar && n == 1) stk.push_back({IT_TN | (cf & CF_ID_MASK), d});
-    } else if (cf & CF_LIT) {
-      stk.push_back({(cf & CF_ID_MASK) | kind, d});
-    }
-  }
-  void create(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig, uint32_t pcf, uint32_t phf,
-              uint32_t d, bool plus_ok, bool lit, bool fat = false, const uint4* h = nullptr,
-              uint32_t rp = 0) {
-    const bool keyed = sig == 0u && (cf & CF_LIT);
-    // (lent signatures, gm_common.h: with CF_LIT clear the field summarises the '+' child's children)
-    const uint32_t lent = ((cf & CF_LIT) ? 0x3Fu : sig) | ix.psig_off;
-    cf = strip(cf, d);
-    const uint64_t wtok = d < REC_TOKS ? (d < n ? toks[d] : 0ull) : 0ull;
-    const uint64_t ptok = d + 1 < n ? toks[d + 1] : 0ull;
-    const bool fat_go = fat && (cf & CF_LIT) && d < n && d < REC_TOKS &&
-                        (uint32_t)wtok == h[0].x && (uint32_t)(wtok >> 32) == h[0].y;
-    if (fat || (!keyed && d < REC_TOKS && !(sig & sig_bit(wtok)))) cf &= ~CF_LIT;
-    pcf = strip(pcf, d + 1);
-    if (d + 1 < REC_TOKS && !(lent & sig_bit(ptok))) pcf &= ~CF_LIT;
-    visit(cf, hf, tw, d, lit, keyed ? IT_KEYED : 0u);
-    if (fat_go)
-      create(h[0].w, h[1].x, h[1].y, h[0].z >> SIG_SHIFT, h[1].z, h[1].w, d + 1, true, true, false,
-             nullptr, rp == 1 ? 2u : 0u);
-    if (!plus_ok || d >= n || !(cf & CF_PLUS)) return;
-    const bool ptw = (pcf & CF_PTW) != 0;
-    if (d + 1 == n && (pcf & CF_TW) && !ptw) {
-      stk.push_back({IT_PLUS | (cf & CF_ID_MASK), d});
-      return;
-    }
-    const uint32_t rpz = ix.rp_on ? ix.rp0.z : NONE;
-    const bool r = rp == 2 && (rpz & CF_ID_MASK) == (pcf & CF_ID_MASK) && (pcf & CF_LIT) && d + 1 < n;
-    if (r) pcf &= ~CF_LIT;
-    visit(pcf & ~CF_PTW, ptw ? NONE : phf, ptw ? phf : NONE, d + 1, false);
-    if (r && (uint32_t)toks[d + 1] == ix.rp0.x && (uint32_t)(toks[d + 1] >> 32) == ix.rp0.y)
-      create(ix.rp0.w, ix.rp1.x, ix.rp1.y, ix.rp0.z >> SIG_SHIFT, ix.rp1.z, ix.rp1.w, d + 2, true, true);
-    if (d + 1 < n && (pcf & CF_PLUS)) stk.push_back({IT_PLUS | (pcf & CF_ID_MASK), d + 1});
-  }
-  // one bucket against (node, key): 1 hit (s, fat, hh filled), 0 the chain ends here (an empty
-  // slot, or -- the rule -- a closed bucket), -1 full of others: on to the next bucket
-  int bucket(uint64_t b, uint32_t node, uint64_t key, uint4 s[2], bool& fat, uint4 hh[2]) {
-    const uint4* q = ix.edges + SLOT_U4 * EBUCKET * b;
-    for (uint32_t j = 0; j < EBUCKET; ++j)
-      if ((q[SLOT_U4 * j].z & CF_ID_MASK) == node && q[SLOT_U4 * j].x == (uint32_t)key &&
-          q[SLOT_U4 * j].y == (uint32_t)(key >> 32)) {
-        s[0] = q[SLOT_U4 * j];
-        s[1] = q[SLOT_U4 * j + 1];
-        fat = j == 0 && (q[SLOT_U4].z & CF_ID_MASK) == FAT_ID;
-        if (fat) {
-          hh[0] = q[SLOT_U4];
-          hh[1] = q[SLOT_U4 + 1];
-        }
-        return 1;
-      }
-    if (q[0].z == NONE || q[SLOT_U4].z == NONE) return 0;
-    const uint32_t off = cb_on ? 0u : 1u;
-    if (slot_closed(q[0].w, q[1].w, off) || slot_closed(q[SLOT_U4].w, q[SLOT_U4 + 1].w, off)) {
-      ++stops;
-      return 0;
-    }
-    return -1;
-  }
-  std::vector<uint32_t> run(const std::string& topic, uint64_t test_mask) {
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)topic.data(), (uint32_t)topic.size(), test_mask, toks, pl, hs, hashed);
-    n = (uint32_t)toks.size();
-    out.clear();
-    stk.clear();
-    for (size_t i = 0; i < n; ++i)
-      if (pl[i] || hs[i]) return out;
-    if (ix.trie_empty) return out;
-    dollar = !topic.empty() && topic[0] == '$';
-    walked = true;
-    const uint4 rh[2] = {ix.rh0, ix.rh1};
-    create(ix.root_cf, dollar ? NONE : ix.root_hf, NONE, ix.root_sig, ix.root_pcf, ix.root_phf, 0,
-           !dollar, false, (ix.rh0.z & CF_ID_MASK) == FAT_ID, rh, 1);
-    Slot P[2];
-    while (!stk.empty() || P[0].busy || P[1].busy) {
-      ++iters;
-      CHECK(iters < 100000, "topic '%s': the walk does not end", topic.c_str());
-      uint32_t shk = NONE;
-      bool stop = false;
-      for (uint32_t j = 0; j < 2; ++j) {
-        Slot& p = P[j];
-        if (p.busy || stk.empty() || stop) continue;
-        if (j > 0 && shk != NONE && (stk.back().first & IT_KIND) == IT_KEYED && stk.back().second == shk) {
-          stop = true;
-          continue;
-        }
-        const auto it = stk.back();
-        stk.pop_back();
-        const uint32_t kind = it.first & IT_KIND;
-        p.busy = true;
-        p.cur = it.first;
-        p.k = it.second;
-        p.side = kind == IT_TN || (kind != IT_PLUS && it.second >= REC_TOKS);
-        if (kind == IT_PLUS) p.key = PLUS_TOK;
-        else if (kind != IT_TN) p.key = toks[it.second];
-        if (j == 0 && ix.ks_on && kind == IT_KEYED && it.second < REC_TOKS) shk = it.second;
-        if (!p.side) p.ia = edge_home(it.first & CF_ID_MASK, p.key, ix.emask, kind == IT_KEYED);
-      }
-      const size_t sh_lo = (shk != NONE && !stk.empty()) ? stk.size() - 1 : stk.size();
-      const uint64_t line0 = P[0].ia;
-      for (uint32_t j = 0; j < 2; ++j) loads += P[j].busy && !P[j].side;
-      for (uint32_t j = 0; j < 2; ++j) {
-        Slot& p = P[j];
-        if (!p.busy) continue;
-        if (p.side) {
-          p.side = false;
-          if ((p.cur & IT_KIND) == IT_TN) {
-            p.busy = false;
-            em(ix.tn_of[p.cur & CF_ID_MASK]);
-          } else {
-            p.ia = edge_home(p.cur & CF_ID_MASK, p.key, ix.emask, (p.cur & IT_KIND) == IT_KEYED);
-          }
-          continue;
-        }
-        uint4 s[2], hh[2];
-        bool fat = false;
-        const int r = bucket(p.ia, p.cur & CF_ID_MASK, p.key, s, fat, hh);
-        if (r == 1) {
-          p.busy = false;
-          create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, p.k + 1, true,
-                 (p.cur & IT_KIND) != IT_PLUS, fat, hh);
-        } else if (r == 0) {
-          p.busy = false;
-        } else {
-          p.ia = (p.ia + 1) & ix.emask;
-        }
-      }
-      if (shk != NONE) {
-        for (size_t i = sh_lo; i < stk.size(); ++i) {
-          if ((stk[i].first & IT_KIND) != IT_KEYED || stk[i].second != shk) continue;
-          const uint32_t node = stk[i].first & CF_ID_MASK;
-          uint4 s[2], hh[2];
-          bool fat = false;
-          const int r = bucket(line0, node, toks[shk], s, fat, hh);
-          if (r != -1) {
-            stk[i] = stk.back();
-            stk.pop_back();
-          }
-          if (r == 1)
-            create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, shk + 1, true, true, fat, hh);
-          break;
-        }
-      }
-    }
-    return out;
-  }
-};
-
-std::string S(uint64_t v) { return std::to_string(v); }
-
-struct Rig {
-  emqxgm_t* h = nullptr;
-  Oracle* orc = new Oracle;
-  std::set<std::string> live;       // the filters in the trie
-  std::vector<std::string> topics;
-  uint32_t hash_bits = 0;
-  int keyed = 1, fat = 1;
-  uint64_t counted = 0;  // delta commits of handles this rig has dropped
+struct Rig : RigBase {
   std::mt19937_64 rng{5};
 
-  void make_handle(bool for_load = false) {
-    emqxgm_cfg cfg{};
-    cfg.word_hash_bits = hash_bits;
-    CHECK(emqxgm_create(&cfg, &h) == 0, "create");
-    CHECK(emqxgm_tune(h, "keyed", keyed) == 0, "tune keyed");
-    // (the tune marks the handle changed, and a snapshot loads into a fresh one only)
-    if (for_load)
-      h->fat_mode = (uint32_t)fat;
-    else
-      CHECK(emqxgm_tune(h, "fat_buckets", fat) == 0, "tune fat");
-    CHECK(emqxgm_tune(h, "delta_commit", 2) == 0, "tune delta");
+  Rig(uint32_t hb, int keyed_mode, int fat_mode) : RigBase(hb, keyed_mode, fat_mode) { tune_key(); }
+  // the rule's tune key: accepted values, rejected values
+  void tune_key() {
     CHECK(emqxgm_tune(h, "closed_buckets", 0) == 0 && emqxgm_tune(h, "closed_buckets", 1) == 0 &&
               emqxgm_tune(h, "closed_buckets", 2) != 0 && emqxgm_tune(h, "closed_buckets", -1) != 0,
           "tune closed_buckets");
   }
-  Rig(uint32_t hb, int keyed_mode, int fat_mode) : hash_bits(hb), keyed(keyed_mode), fat(fat_mode) {
-    make_handle();
-  }
-  ~Rig() {
-    g_deltas += counted + deltas();
-    emqxgm_destroy(h);
-    delete orc;
-  }
-  void add(const std::string& f) {
-    CHECK(emqxgm_trie_insert(h, (const uint8_t*)f.data(), (uint32_t)f.size(), nullptr) == 0, "ins");
-    orc->add(f, 1);
-    live.insert(f);
-  }
-  void del(const std::string& f) {
-    CHECK(emqxgm_trie_delete(h, (const uint8_t*)f.data(), (uint32_t)f.size()) == 0, "del");
-    ref_trie_delete(orc->r, (const uint8_t*)f.data(), (uint32_t)f.size());
-    live.erase(f);
-  }
-  uint64_t deltas() {
-    emqxgm_stats st{};
-    emqxgm_get_stats(h, &st);
-    return st.delta_commits;
-  }
-  const TrieModel& m() const { return h->tm; }
 
-  // the node at the end of a path of words ("" = the root), NONE when it is not in the trie
-  uint32_t node_of(const std::string& path) {
-    if (path.empty()) return 0;
-    std::vector<uint64_t> toks;
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)path.data(), (uint32_t)path.size(), h->test_mask, toks, pl, hs, hashed);
-    uint32_t cur = 0;
-    for (size_t w = 0; w < toks.size(); ++w) {
-      const uint32_t* v = h->tm.emap.find(cur, pl[w] ? PLUS_TOK : toks[w]);
-      if (!v) return NONE;
-      cur = *v;
-    }
-    return cur;
-  }
-  uint64_t word_tok(const std::string& w) {
-    std::vector<uint64_t> toks;
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)w.data(), (uint32_t)w.size(), h->test_mask, toks, pl, hs, hashed);
-    return toks[0];
-  }
   // every proper prefix of a live filter that ends at a node (its words before a trailing '#')
   std::vector<std::string> prefixes() {
     std::set<std::string> ps;
@@ -351,61 +108,29 @@ struct Rig {
     CHECK(ix.rh1.w != EDGE_CLOSED || (ix.rh0.w & CF_PLUS), "%s: a mark on the root's half", what);
   }
 
-  void rows(const char* what) {
-    std::string tb;
-    std::vector<uint32_t> toff(1, 0);
-    for (const auto& t : topics) {
-      tb += t;
-      toff.push_back((uint32_t)tb.size());
-    }
-    std::vector<uint64_t> row(topics.size() + 1);
-    std::vector<uint32_t> rex(topics.size());
-    uint32_t* ids = nullptr;
-    uint64_t nids = 0;
-    ref_match_batch(orc->r, (const uint8_t*)tb.data(), toff.data(), topics.size(), 1, row.data(), &ids,
-                    &nids, rex.data());
-    const DevIndex& ix = h->cur->ix;
-    for (size_t i = 0; i < topics.size(); ++i) {
-      CpuWalk w(ix);
-      std::vector<uint32_t> base = w.run(topics[i], h->test_mask);
-      std::sort(base.begin(), base.end());
+  // the invariants, then the rows: the plain reader's, the restated walk's with the rule off and
+  // on (closed_rules), the oracle's
+  void checks(const char* what) {
+    marks(what);
+    rows(what, [&](const std::string& t, const std::vector<uint32_t>& base) {
       for (int on = 0; on < 2; ++on) {
-        SlotWalk sw(ix, on != 0);
-        std::vector<uint32_t> got = sw.run(topics[i], h->test_mask);
-        std::sort(got.begin(), got.end());
-        CHECK(got == base, "%s: topic '%s': closed_buckets %d: %zu ids, the plain reader %zu", what,
-              topics[i].c_str(), on, got.size(), base.size());
+        const SlotWalk sw = slot_walk(closed_rules(h->cur->ix, on != 0), what, t, base,
+                                      on ? "closed_buckets 1" : "closed_buckets 0");
         CHECK(on || sw.stops == 0, "%s: the rule applied while off", what);
         g_loads[on] += sw.loads;
         g_iters[on] += sw.iters;
         if (on) g_stops += sw.stops;
       }
-      std::vector<std::string> gs, ws;
-      for (uint32_t f : base) {
-        const bool verify = (ix.fvbits[f >> 5] >> (f & 31)) & 1u;
-        const std::string fs = filter_str(h, f);
-        if (!verify || mqtt_match(topics[i], fs)) gs.push_back(fs);
-      }
-      for (uint64_t j = row[i]; j < row[i + 1]; ++j) ws.push_back(orc->names[ids[j]]);
-      std::sort(gs.begin(), gs.end());
-      std::sort(ws.begin(), ws.end());
-      CHECK(gs == ws, "%s: topic '%s': %zu vs %zu filters", what, topics[i].c_str(), gs.size(), ws.size());
-      ++g_rows;
-    }
-    ref_free(ids);
+    });
   }
 
   // commit and check; delta: the commit must be a delta commit (with collision tokens one may be
   // declined -- two filters at one node -- and built in full).  Returns the buckets the delta
   // opened, -1 after a full build.
   int64_t step(const char* what, bool delta = true) {
-    const uint64_t d0 = deltas();
     const std::vector<uint64_t> open0 = h->tm.valid ? h->tm.open : std::vector<uint64_t>();
-    CHECK(emqxgm_commit(h, nullptr) == 0, "%s: commit: %s", what, h->err.c_str());
-    ++g_commits;
     int64_t opened = -1;
-    if (delta && hash_bits == 0) CHECK(deltas() == d0 + 1, "%s: not a delta commit", what);
-    if (delta && deltas() == d0 + 1) {
+    if (commit(what, delta)) {
       opened = 0;
       CHECK(open0.size() == h->tm.open.size(), "%s: bitmap resized by a delta", what);
       for (size_t i = 0; i < open0.size(); ++i) {
@@ -414,8 +139,7 @@ struct Rig {
       }
       g_opened += (uint64_t)opened;
     }
-    marks(what);
-    rows(what);
+    checks(what);
     return opened;
   }
 
@@ -536,8 +260,7 @@ struct Rig {
           (unsigned long long)(st.bg_builds - st0.bg_builds),
           (unsigned long long)(st.catchup_changes - st0.catchup_changes));
     ++g_commits;
-    marks(what);
-    rows(what);
+    checks(what);
     CHECK(emqxgm_tune(h, "bg_build", 0) == 0 && emqxgm_tune(h, "delta_max", 0) == 0 &&
               emqxgm_tune(h, "delta_commit", 2) == 0 && emqxgm_tune(h, "bg_delay_ms", 0) == 0,
           "tune");
@@ -554,6 +277,7 @@ struct Rig {
     counted += deltas();
     emqxgm_destroy(h);
     make_handle(true);
+    tune_key();
     CHECK(emqxgm_snapshot_load(h, path) == 0, "%s: load: %s", what, h->err.c_str());
     unlink(path);
     // the loaded bits are derived from the placement: never a bucket closed that an edge passes
@@ -561,8 +285,7 @@ struct Rig {
     CHECK(open0.size() == h->tm.open.size(), "%s: bitmap size", what);
     for (size_t i = 0; i < open0.size(); ++i)
       CHECK((h->tm.open[i] & ~open0[i]) == 0, "%s: the load opened a bucket", what);
-    marks(what);
-    rows(what);
+    checks(what);
   }
 
   void churn() {
@@ -692,7 +415,7 @@ int count(const char* ffile, const char* tfile) {
   uint64_t loads[2] = {0, 0}, iters[2] = {0, 0}, stops = 0;
   for (const auto& t : r.topics)
     for (int on = 0; on < 2; ++on) {
-      SlotWalk sw(r.h->cur->ix, on != 0);
+      SlotWalk sw(r.h->cur->ix, closed_rules(r.h->cur->ix, on != 0));
       sw.run(t, r.h->test_mask);
       loads[on] += sw.loads;
       iters[on] += sw.walked ? std::max<uint64_t>(sw.iters, 1) : 0;

@@ -1,7 +1,18 @@
-// harness_walk.h -- TEST INFRASTRUCTURE shared by the host harnesses (harness.cpp, bg_harness.cpp):
-// the engine's host code itself (gm_engine.cpp, included), the walk of gm_walk.inc and the probe
-// of k_exact restated on the CPU over the committed tables, emqx_topic:match/2 on strings, and
-// the oracle's C++ restatement (oracle/ref_trie.cpp) as the checker.
+// harness_walk.h -- TEST INFRASTRUCTURE shared by the host harnesses (harness.cpp, bg_harness.cpp
+// and, through harness_rig.h, psig_harness.cpp, rph_harness.cpp, closed_harness.cpp): the
+// engine's host code itself (gm_engine.cpp, included), the walk of gm_walk.inc and the probe of
+// k_exact restated on the CPU over the committed tables, emqx_topic:match/2 on strings, and the
+// oracle's C++ restatement (oracle/ref_trie.cpp) as the checker.
+//
+// Two readers of the committed edge table live here, and only here:
+//   * CpuWalk, the plain reader: one probe after the other, every bucket of a chain up to an
+//     empty slot, and none of the walk's rules;
+//   * SlotWalk, the one restatement of k_walk's iteration (two probe slots, one bucket per slot
+//     and round trip), with the rules of gm_walk.inc behind the switches of WalkRules: lent
+//     signatures, the root's '+' half, the shared line of keyed siblings, closed buckets.
+// They share what WalkBase holds -- tokens, the item stack, what a state lists -- and nothing
+// that creates a state's children or probes the table: a harness compares the rows of one with
+// the rows of the other.
 #pragma once
 #include <stdio.h>
 
@@ -67,8 +78,8 @@ std::string filter_str(emqxgm* h, uint32_t id) {
   return std::string((const char*)h->pool.data() + f.off, f.len);
 }
 
-// The walk of gm_walk.inc over the committed tables, on the CPU.
-struct CpuWalk {
+// What the two readers below share: a topic's tokens, the item stack, what a state lists.
+struct WalkBase {
   const DevIndex& ix;
   std::vector<uint64_t> toks;
   uint32_t n = 0;
@@ -78,7 +89,7 @@ struct CpuWalk {
   static constexpr uint32_t IT_PLUS = 0x80000000u, IT_TN = 0x40000000u;
   static constexpr uint32_t IT_KEYED = IT_PLUS | IT_TN, IT_KIND = IT_PLUS | IT_TN;
 
-  explicit CpuWalk(const DevIndex& x) : ix(x) {}
+  explicit WalkBase(const DevIndex& x) : ix(x) {}
   void em(uint32_t v) {
     if (v == NONE) return;
     if (v & LIST_MULTI) {
@@ -101,6 +112,26 @@ struct CpuWalk {
       stk.push_back({(cf & CF_ID_MASK) | kind, d});
     }
   }
+  // tokenises the topic and clears the output; false when no walk starts: a wildcard topic
+  // name -> [] (emqx_trie.erl:157-166), or an empty trie
+  bool begin(const std::string& topic, uint64_t test_mask) {
+    std::vector<uint8_t> pl, hs;
+    bool hashed;
+    tokenize((const uint8_t*)topic.data(), (uint32_t)topic.size(), test_mask, toks, pl, hs, hashed);
+    n = (uint32_t)toks.size();
+    out.clear();
+    stk.clear();
+    for (size_t i = 0; i < n; ++i)
+      if (pl[i] || hs[i]) return false;
+    if (ix.trie_empty) return false;
+    dollar = !topic.empty() && topic[0] == '$';
+    return true;
+  }
+};
+
+// The walk of gm_walk.inc over the committed tables, on the CPU: the plain reader.
+struct CpuWalk : WalkBase {
+  using WalkBase::WalkBase;
   // fat: the state's only literal child comes with it in {h0, h1} (gm_common.h FAT_ID)
   void create(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig, uint32_t pcf, uint32_t phf,
               uint32_t d, bool plus_ok, bool lit, bool fat = false, const uint4* h = nullptr) {
@@ -147,16 +178,7 @@ struct CpuWalk {
     }
   }
   std::vector<uint32_t> run(const std::string& topic, uint64_t test_mask) {
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)topic.data(), (uint32_t)topic.size(), test_mask, toks, pl, hs, hashed);
-    n = (uint32_t)toks.size();
-    out.clear();
-    stk.clear();
-    for (size_t i = 0; i < n; ++i)
-      if (pl[i] || hs[i]) return out;  // wildcard topic name -> [] (emqx_trie.erl:157-166)
-    if (ix.trie_empty) return out;
-    dollar = !topic.empty() && topic[0] == '$';
+    if (!begin(topic, test_mask)) return out;
     const uint4 rh[2] = {ix.rh0, ix.rh1};
     create(ix.root_cf, dollar ? NONE : ix.root_hf, NONE, ix.root_sig, ix.root_pcf, ix.root_phf, 0,
            !dollar, false, (ix.rh0.z & CF_ID_MASK) == FAT_ID, rh);
@@ -177,6 +199,180 @@ struct CpuWalk {
       if (hit)
         create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, k + 1, true,
                kind != IT_PLUS, fat, hh);
+    }
+    return out;
+  }
+};
+
+// The rules of gm_walk.inc that SlotWalk has, each behind a switch.  The defaults are the
+// committed index's, as launch_walk reads them (gm_kernels.hip); a harness overrides the ones it
+// compares.
+struct WalkRules {
+  bool lent;  // lent signatures drop literal probes under a carried '+' child (tune "plus_sig")
+  bool rp;    // the root's '+' half rides in the arguments (tune "root_plus_half")
+  bool ks;    // keyed siblings of one level are decided from one line (tune "keyed_share")
+  bool cb;    // a missed lookup ends at a closed bucket (tune "closed_buckets")
+  explicit WalkRules(const DevIndex& ix)
+      : lent(ix.psig_off == 0u), rp(ix.rp_on != 0u), ks(ix.ks_on != 0u), cb(ix.cb_on != 0u) {}
+};
+
+// k_walk's iteration restated: the fill and resolve order of gm_walk.inc with NS = 2 slots, as
+// the compact one-lane-per-topic walks and the census have it.
+struct SlotWalk : WalkBase {
+  const WalkRules rules;
+  uint64_t loads = 0, iters = 0;  // bucket loads, iterations of the lane
+  uint64_t stops = 0;             // lookups ended at a closed bucket
+  uint64_t rp_hits = 0;           // states created from the copy rp0/rp1
+  uint64_t shared = 0;            // keyed siblings decided from slot 0's line
+  bool walked = false;  // the topic reached the walk (not a wildcard name, the trie not empty)
+  struct Slot {
+    bool busy = false, side = false;
+    uint32_t cur = 0, k = 0;
+    uint64_t key = 0, ia = 0;
+  };
+
+  SlotWalk(const DevIndex& x, const WalkRules& r) : WalkBase(x), rules(r) {}
+  explicit SlotWalk(const DevIndex& x) : SlotWalk(x, WalkRules(x)) {}
+  // rp: 1 = the root's state, 2 = its fat half's (gm_walk.inc create RP)
+  void create(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig, uint32_t pcf, uint32_t phf,
+              uint32_t d, bool plus_ok, bool lit, bool fat = false, const uint4* h = nullptr,
+              uint32_t rp = 0) {
+    const bool keyed = sig == 0u && (cf & CF_LIT);
+    // (lent signatures, gm_common.h: with CF_LIT clear the field summarises the '+' child's children)
+    const uint32_t lent = ((cf & CF_LIT) || !rules.lent) ? 0x3Fu : sig;
+    cf = strip(cf, d);
+    const uint64_t wtok = d < REC_TOKS ? (d < n ? toks[d] : 0ull) : 0ull;
+    const uint64_t ptok = d + 1 < n ? toks[d + 1] : 0ull;
+    const bool fat_go = fat && (cf & CF_LIT) && d < n && d < REC_TOKS &&
+                        (uint32_t)wtok == h[0].x && (uint32_t)(wtok >> 32) == h[0].y;
+    if (fat || (!keyed && d < REC_TOKS && !(sig & sig_bit(wtok)))) cf &= ~CF_LIT;
+    pcf = strip(pcf, d + 1);
+    if (d + 1 < REC_TOKS && !(lent & sig_bit(ptok))) pcf &= ~CF_LIT;
+    visit(cf, hf, tw, d, lit, keyed ? IT_KEYED : 0u);
+    if (fat_go)
+      create(h[0].w, h[1].x, h[1].y, h[0].z >> SIG_SHIFT, h[1].z, h[1].w, d + 1, true, true, false,
+             nullptr, rp == 1 ? 2u : 0u);
+    if (!plus_ok || d >= n || !(cf & CF_PLUS)) return;
+    const bool ptw = (pcf & CF_PTW) != 0;
+    if (d + 1 == n && (pcf & CF_TW) && !ptw) {
+      stk.push_back({IT_PLUS | (cf & CF_ID_MASK), d});
+      return;
+    }
+    const uint32_t rpz = rules.rp ? ix.rp0.z : NONE;  // (launch_walk: the tune masks the copy)
+    const bool r = rp == 2 && (rpz & CF_ID_MASK) == (pcf & CF_ID_MASK) && (pcf & CF_LIT) && d + 1 < n;
+    if (r) pcf &= ~CF_LIT;
+    visit(pcf & ~CF_PTW, ptw ? NONE : phf, ptw ? phf : NONE, d + 1, false);
+    if (r && (uint32_t)toks[d + 1] == ix.rp0.x && (uint32_t)(toks[d + 1] >> 32) == ix.rp0.y) {
+      ++rp_hits;
+      create(ix.rp0.w, ix.rp1.x, ix.rp1.y, ix.rp0.z >> SIG_SHIFT, ix.rp1.z, ix.rp1.w, d + 2, true, true);
+    }
+    if (d + 1 < n && (pcf & CF_PLUS)) stk.push_back({IT_PLUS | (pcf & CF_ID_MASK), d + 1});
+  }
+  // one bucket against (node, key): 1 hit (s, fat, hh filled), 0 the chain ends here (an empty
+  // slot, or -- rules.cb -- a closed bucket), -1 full of others: on to the next bucket
+  int bucket(uint64_t b, uint32_t node, uint64_t key, uint4 s[2], bool& fat, uint4 hh[2]) {
+    const uint4* q = ix.edges + SLOT_U4 * EBUCKET * b;
+    for (uint32_t j = 0; j < EBUCKET; ++j)
+      if ((q[SLOT_U4 * j].z & CF_ID_MASK) == node && q[SLOT_U4 * j].x == (uint32_t)key &&
+          q[SLOT_U4 * j].y == (uint32_t)(key >> 32)) {
+        s[0] = q[SLOT_U4 * j];
+        s[1] = q[SLOT_U4 * j + 1];
+        fat = j == 0 && (q[SLOT_U4].z & CF_ID_MASK) == FAT_ID;
+        if (fat) {
+          hh[0] = q[SLOT_U4];
+          hh[1] = q[SLOT_U4 + 1];
+        }
+        return 1;
+      }
+    if (q[0].z == NONE || q[SLOT_U4].z == NONE) return 0;
+    const uint32_t off = rules.cb ? 0u : 1u;
+    if (slot_closed(q[0].w, q[1].w, off) || slot_closed(q[SLOT_U4].w, q[SLOT_U4 + 1].w, off)) {
+      ++stops;
+      return 0;
+    }
+    return -1;
+  }
+  std::vector<uint32_t> run(const std::string& topic, uint64_t test_mask) {
+    if (!begin(topic, test_mask)) return out;
+    walked = true;
+    const uint4 rh[2] = {ix.rh0, ix.rh1};
+    create(ix.root_cf, dollar ? NONE : ix.root_hf, NONE, ix.root_sig, ix.root_pcf, ix.root_phf, 0,
+           !dollar, false, (ix.rh0.z & CF_ID_MASK) == FAT_ID, rh, 1);
+    Slot P[2];
+    while (!stk.empty() || P[0].busy || P[1].busy) {
+      ++iters;
+      CHECK(iters < 100000, "topic '%s': the walk does not end", topic.c_str());
+      // ---- fill ----
+      uint32_t shk = NONE;
+      bool stop = false;
+      for (uint32_t j = 0; j < 2; ++j) {
+        Slot& p = P[j];
+        if (p.busy || stk.empty() || stop) continue;
+        if (j > 0 && shk != NONE && (stk.back().first & IT_KIND) == IT_KEYED && stk.back().second == shk) {
+          stop = true;  // a keyed sibling of slot 0's probe stays on the stack
+          continue;
+        }
+        const auto it = stk.back();
+        stk.pop_back();
+        const uint32_t kind = it.first & IT_KIND;
+        p.busy = true;
+        p.cur = it.first;
+        p.k = it.second;
+        p.side = kind == IT_TN || (kind != IT_PLUS && it.second >= REC_TOKS);
+        if (kind == IT_PLUS) p.key = PLUS_TOK;
+        else if (kind != IT_TN) p.key = toks[it.second];
+        if (j == 0 && rules.ks && kind == IT_KEYED && it.second < REC_TOKS) shk = it.second;
+        if (!p.side) p.ia = edge_home(it.first & CF_ID_MASK, p.key, ix.emask, kind == IT_KEYED);
+      }
+      const size_t sh_lo = (shk != NONE && !stk.empty()) ? stk.size() - 1 : stk.size();
+      const uint64_t line0 = P[0].ia;  // slot 0's line of this round trip
+      for (uint32_t j = 0; j < 2; ++j) loads += P[j].busy && !P[j].side;
+      // ---- resolve ----
+      for (uint32_t j = 0; j < 2; ++j) {
+        Slot& p = P[j];
+        if (!p.busy) continue;
+        if (p.side) {
+          p.side = false;
+          if ((p.cur & IT_KIND) == IT_TN) {
+            p.busy = false;
+            em(ix.tn_of[p.cur & CF_ID_MASK]);
+          } else {
+            p.ia = edge_home(p.cur & CF_ID_MASK, p.key, ix.emask, (p.cur & IT_KIND) == IT_KEYED);
+          }
+          continue;
+        }
+        uint4 s[2], hh[2];
+        bool fat = false;
+        const int r = bucket(p.ia, p.cur & CF_ID_MASK, p.key, s, fat, hh);
+        if (r == 1) {
+          p.busy = false;
+          create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, p.k + 1, true,
+                 (p.cur & IT_KIND) != IT_PLUS, fat, hh);
+        } else if (r == 0) {
+          p.busy = false;
+        } else {
+          p.ia = (p.ia + 1) & ix.emask;
+        }
+      }
+      // ---- the late match: the first keyed item of slot 0's level against slot 0's line ----
+      if (shk != NONE) {
+        for (size_t i = sh_lo; i < stk.size(); ++i) {
+          if ((stk[i].first & IT_KIND) != IT_KEYED || stk[i].second != shk) continue;
+          const uint32_t node = stk[i].first & CF_ID_MASK;
+          CHECK(edge_home(node, toks[shk], ix.emask, true) == line0, "keyed siblings, two homes");
+          uint4 s[2], hh[2];
+          bool fat = false;
+          const int r = bucket(line0, node, toks[shk], s, fat, hh);
+          if (r != -1) {
+            ++shared;
+            stk[i] = stk.back();
+            stk.pop_back();
+          }
+          if (r == 1)
+            create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, shk + 1, true, true, fat, hh);
+          break;
+        }
+      }
     }
     return out;
   }

@@ -1,8 +1,10 @@
 // psig_harness.cpp -- TEST INFRASTRUCTURE: the lent-signature invariant of the edge table
 // (gm_common.h "Lent signatures") after a full build and after every step of a delta churn.
 //
-// Built by tests/test_psig_host.py with g++ -fsanitize=address,undefined against the fake HIP
-// runtime of this directory, like harness.cpp.  After every commit it scans every live node's
+// Built by tests/test_psig_host.py (tests/host_build.py) under ASan + UBSan against the fake HIP
+// runtime of this directory, like harness.cpp; the rig is harness_rig.h's.  It runs no SlotWalk
+// (harness_walk.h): the filter it guards only removes probes, so the rows of the plain reader
+// are the check.  After every commit it scans every live node's
 // slot in the committed device tables (the root's half in the arguments and the root's own
 // signature included):
 //   * the slot equals what the model gives for its node (a delta left no stale slot behind);
@@ -13,63 +15,19 @@
 // and walks every probe topic on the CPU with the reader that ignores lent bits
 // (harness_walk.h), whose rows must stay equal to the oracle's.
 // Prints "OK <commits> <delta commits> <slots scanned> <lending slots> <row checks>".
-#include "harness_walk.h"
+#include "harness_rig.h"
 
 namespace {
 
-uint64_t g_commits = 0, g_deltas = 0, g_slots = 0, g_lending = 0, g_rows = 0;
+uint64_t g_slots = 0, g_lending = 0;
 
-struct Rig {
-  emqxgm_t* h = nullptr;
-  Oracle orc;
-  std::vector<std::string> topics;
-  uint32_t hash_bits = 0;
-
-  Rig(uint32_t hb, int keyed_mode, int fat) : hash_bits(hb) {
-    emqxgm_cfg cfg{};
-    cfg.word_hash_bits = hb;
-    CHECK(emqxgm_create(&cfg, &h) == 0, "create");
-    CHECK(emqxgm_tune(h, "keyed", keyed_mode) == 0, "tune keyed");
-    CHECK(emqxgm_tune(h, "fat_buckets", fat) == 0, "tune fat");
-    CHECK(emqxgm_tune(h, "delta_commit", 2) == 0, "tune delta");  // every delta that fits is patched
-  }
-  ~Rig() {
-    g_deltas += deltas();
-    emqxgm_destroy(h);
-  }
-  void add(const std::string& f) {
-    CHECK(emqxgm_trie_insert(h, (const uint8_t*)f.data(), (uint32_t)f.size(), nullptr) == 0, "ins");
-    orc.add(f, 1);
-  }
-  void del(const std::string& f) {
-    CHECK(emqxgm_trie_delete(h, (const uint8_t*)f.data(), (uint32_t)f.size()) == 0, "del");
-    ref_trie_delete(orc.r, (const uint8_t*)f.data(), (uint32_t)f.size());
-  }
-  uint64_t deltas() {
-    emqxgm_stats st{};
-    emqxgm_get_stats(h, &st);
-    return st.delta_commits;
-  }
-  // the model's node at the end of a path of levels ("+" = the '+' edge), 0 if absent
+struct Rig : RigBase {
+  using RigBase::RigBase;
+  // the node at the end of a path that is in the trie
   uint32_t node(const std::string& path) {
-    std::vector<uint64_t> tk;
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)path.data(), (uint32_t)path.size(), h->test_mask, tk, pl, hs, hashed);
-    uint32_t cur = 0;
-    for (size_t w = 0; w < tk.size(); ++w) {
-      const uint32_t* v = h->tm.emap.find(cur, pl[w] ? PLUS_TOK : tk[w]);
-      if (!v) return 0;
-      cur = *v;
-    }
-    return cur;
-  }
-  uint64_t token(const std::string& word) {
-    std::vector<uint64_t> tk;
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)word.data(), (uint32_t)word.size(), h->test_mask, tk, pl, hs, hashed);
-    return tk[0];
+    const uint32_t c = node_of(path);
+    CHECK(c != NONE, "no node at '%s'", path.c_str());
+    return c;
   }
   // the committed slot of node c (the root's half: the arguments); nullptr for the root
   const uint4* slot(uint32_t c, uint4 tmp[2]) {
@@ -131,50 +89,14 @@ struct Rig {
     }
   }
 
-  void rows(const char* what) {
-    std::string tb;
-    std::vector<uint32_t> toff(1, 0);
-    for (const auto& t : topics) {
-      tb += t;
-      toff.push_back((uint32_t)tb.size());
-    }
-    std::vector<uint64_t> row(topics.size() + 1);
-    std::vector<uint32_t> rex(topics.size());
-    uint32_t* ids = nullptr;
-    uint64_t nids = 0;
-    ref_match_batch(orc.r, (const uint8_t*)tb.data(), toff.data(), topics.size(), 1, row.data(), &ids,
-                    &nids, rex.data());
-    const DevIndex& ix = h->cur->ix;
-    for (size_t i = 0; i < topics.size(); ++i) {
-      CpuWalk w(ix);
-      std::vector<std::string> gs, ws;
-      for (uint32_t f : w.run(topics[i], h->test_mask)) {
-        const bool verify = (ix.fvbits[f >> 5] >> (f & 31)) & 1u;
-        const std::string fs = filter_str(h, f);
-        if (!verify || mqtt_match(topics[i], fs)) gs.push_back(fs);
-      }
-      for (uint64_t j = row[i]; j < row[i + 1]; ++j) ws.push_back(orc.names[ids[j]]);
-      std::sort(gs.begin(), gs.end());
-      std::sort(ws.begin(), ws.end());
-      CHECK(gs == ws, "%s: topic '%s': %zu vs %zu filters", what, topics[i].c_str(), gs.size(), ws.size());
-      ++g_rows;
-    }
-    ref_free(ids);
-  }
-
   // commit, then every check; delta: the commit must have patched the tables in place
   void step(const char* what, bool delta = true) {
-    const uint64_t d0 = deltas();
-    CHECK(emqxgm_commit(h, nullptr) == 0, "%s: commit: %s", what, h->err.c_str());
-    ++g_commits;
-    // (collision tokens put several keys on one node: such a delta is declined and rebuilt)
-    if (delta && hash_bits == 0) CHECK(deltas() == d0 + 1, "%s: not a delta commit", what);
+    commit(what, delta);
     scan(what);
-    rows(what);
+    // (no SlotWalk here: the rows are the plain reader's, which ignores lent bits)
+    rows(what, [](const std::string&, const std::vector<uint32_t>&) {});
   }
 };
-
-std::string S(uint64_t v) { return std::to_string(v); }
 
 // A cfg3-shaped trie (workloads/gen.cpp gen_cfg3: 4 sites x 8 devices, its five patterns) and
 // the churn of its device states.
@@ -239,7 +161,7 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     const uint32_t c = r.node(D);
     std::string w;
     for (int i = 7; i < 13 && w.empty(); ++i)
-      if (!(r.field(c) & sig_bit(r.token("q" + S(i))))) w = "q" + S(i);
+      if (!(r.field(c) & sig_bit(r.word_tok("q" + S(i))))) w = "q" + S(i);
     if (exact) {
       CHECK(c && r.h->tm.nlit[c] == 0 && r.h->tm.pchild[c], "D shape");
       CHECK(!w.empty(), "no word of a class that is still clear");
@@ -247,7 +169,7 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     if (w.empty()) w = "q7";
     r.add(D + "/+/" + w);
     r.step("literal child under D/+");
-    if (exact) CHECK(r.field(c) & sig_bit(r.token(w)), "the new child's class is not lent");
+    if (exact) CHECK(r.field(c) & sig_bit(r.word_tok(w)), "the new child's class is not lent");
     r.del(D + "/+/" + w);
     r.step("literal child under D/+ deleted");
   }
@@ -259,7 +181,7 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     if (exact) CHECK(c && r.h->tm.nlit[c] == 0 && lent != 0, "D shape");
     r.add(D + "/lit/x");
     r.step("first literal child");
-    if (exact) CHECK(r.field(c) == sig_bit(r.token("lit")), "own signature after the first literal child");
+    if (exact) CHECK(r.field(c) == sig_bit(r.word_tok("lit")), "own signature after the first literal child");
     r.del(D + "/lit/x");
     r.step("last literal child deleted");
     if (exact) CHECK(r.field(c) == lent, "lent signature back after the last literal child");
@@ -271,13 +193,13 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     if (exact) CHECK(c && r.h->tm.pchild[c] == 0 && r.field(c) == 0, "D shape");
     r.add(D + "/+/3");
     r.step("'+' child added");
-    if (exact) CHECK(r.field(c) == sig_bit(r.token("3")), "a new '+' child's signature is lent");
+    if (exact) CHECK(r.field(c) == sig_bit(r.word_tok("3")), "a new '+' child's signature is lent");
     r.del(D + "/+/3");
     r.step("'+' child deleted");
     if (exact) CHECK(r.field(c) == 0, "no '+' child, no lent bits");
     r.add(D + "/+/4");  // (a new '+' node: the old one's bits must not come back)
     r.step("'+' child added again");
-    if (exact) CHECK(r.field(c) == sig_bit(r.token("4")), "the new '+' child's signature");
+    if (exact) CHECK(r.field(c) == sig_bit(r.word_tok("4")), "the new '+' child's signature");
   }
   // -- a keyed parent loses all its literal children: it lends, it does not write the keyed 0
   {
@@ -289,7 +211,7 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     r.step("keyed parent without literal children");
     if (exact) {
       CHECK(r.h->tm.nlit[c] == 0 && (keyed_mode != 2 || r.h->tm.keyed[c]), "D shape");
-      CHECK(r.field(c) == (sig_bit(r.token("5")) | sig_bit(r.token("11"))), "a keyed node lends");
+      CHECK(r.field(c) == (sig_bit(r.word_tok("5")) | sig_bit(r.word_tok("11"))), "a keyed node lends");
     }
     r.add(D + "/a/z");
     r.step("keyed parent with a literal child again");
@@ -301,14 +223,14 @@ void run_cfg3(uint32_t hash_bits, int keyed_mode, int fat) {
     const uint32_t c = r.node(D), g = r.node(D + "/only");
     if (exact && fat) {
       CHECK(c && g && r.h->tm.fchild[c] == g && r.h->tm.half[g], "no fat node");
-      CHECK(r.field(g) == sig_bit(r.token("7")), "the half lends");
+      CHECK(r.field(g) == sig_bit(r.word_tok("7")), "the half lends");
     }
     r.add(D + "/only/+/9");
     r.step("literal child under a half's '+' child");
-    if (exact) CHECK(r.field(g) == (sig_bit(r.token("7")) | sig_bit(r.token("9"))), "the half's lent bits");
+    if (exact) CHECK(r.field(g) == (sig_bit(r.word_tok("7")) | sig_bit(r.word_tok("9"))), "the half's lent bits");
     r.add(D + "/other");
     r.step("the half moves out");
-    if (exact) CHECK(!r.h->tm.half[g] && r.field(g) == (sig_bit(r.token("7")) | sig_bit(r.token("9"))),
+    if (exact) CHECK(!r.h->tm.half[g] && r.field(g) == (sig_bit(r.word_tok("7")) | sig_bit(r.word_tok("9"))),
                      "the moved half still lends");
   }
   // -- and a full build of the churned registry
@@ -327,17 +249,17 @@ void run_root(uint32_t hash_bits) {
   r.step("root build", false);
   if (exact) {
     CHECK(r.h->tm.nlit[0] == 0 && !(r.h->cur->ix.root_cf & CF_LIT), "root shape");
-    CHECK(r.field(0) == (sig_bit(r.token("a")) | sig_bit(r.token("b"))), "the root lends");
+    CHECK(r.field(0) == (sig_bit(r.word_tok("a")) | sig_bit(r.word_tok("b"))), "the root lends");
   }
   r.add("+/zz");
   r.step("literal child under the root's '+' child");
-  if (exact) CHECK(r.field(0) & sig_bit(r.token("zz")), "root_sig follows");
+  if (exact) CHECK(r.field(0) & sig_bit(r.word_tok("zz")), "root_sig follows");
   r.add("lit/q");
   r.step("the root's first literal child");
-  if (exact) CHECK((r.h->cur->ix.root_cf & CF_LIT) && r.field(0) == sig_bit(r.token("lit")), "root's own");
+  if (exact) CHECK((r.h->cur->ix.root_cf & CF_LIT) && r.field(0) == sig_bit(r.word_tok("lit")), "root's own");
   r.del("lit/q");
   r.step("the root's last literal child deleted");
-  if (exact) CHECK(!(r.h->cur->ix.root_cf & CF_LIT) && (r.field(0) & sig_bit(r.token("zz"))), "root lends again");
+  if (exact) CHECK(!(r.h->cur->ix.root_cf & CF_LIT) && (r.field(0) & sig_bit(r.word_tok("zz"))), "root lends again");
 }
 
 }  // namespace

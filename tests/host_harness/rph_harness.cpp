@@ -1,244 +1,33 @@
 // rph_harness.cpp -- TEST INFRASTRUCTURE: the root's '+' half (gm_kernels.h DevIndex::rp0/rp1) and
 // the shared line of keyed siblings (gm_walk.inc SHARE), on the CPU.
 //
-// Built by tests/test_rph_host.py with g++ -fsanitize=address,undefined against the fake HIP
-// runtime of this directory, like psig_harness.cpp.  After a full build and after every step of a
-// delta churn it checks that
+// Built by tests/test_rph_host.py (tests/host_build.py) under ASan + UBSan against the fake HIP
+// runtime of this directory, like psig_harness.cpp; the rig is harness_rig.h's, the restated walk
+// harness_walk.h's SlotWalk, run with the switches rp and ks in all four combinations and with
+// lent and cb off.  After a full build and after every step of a delta churn it checks that
 //   * rp0/rp1 is absent, or equals node_slot of the only live literal child H of the '+' child p
 //     of the root's half G -- and equals H's slot in the committed table (the copy is a cache);
 //     where a step says so, that it is present (a build with one such child) or absent (a second
 //     literal child under G/+ clears it in that same commit);
-//   * a restatement of k_walk's iteration -- two probe slots filled from the LIFO, one bucket per
+//   * the restatement of k_walk's iteration -- two probe slots filled from the LIFO, one bucket per
 //     slot and round trip, resolves in slot order, then the late match -- returns the same rows
 //     with the two rules on and off, equal to the rows of the reader that knows neither
-//     (harness_walk.h, unchanged) and to the oracle's.
+//     (harness_walk.h CpuWalk) and to the oracle's.
 // Prints "OK <commits> <delta commits> <copies present> <copy hits> <shared items> <row checks>".
-#include "harness_walk.h"
+#include "harness_rig.h"
 
 namespace {
 
-uint64_t g_commits = 0, g_deltas = 0, g_present = 0, g_rp_hits = 0, g_shared = 0, g_rows = 0;
+uint64_t g_present = 0, g_rp_hits = 0, g_shared = 0;
 uint64_t g_loads[2] = {0, 0}, g_iters[2] = {0, 0};
 
-// k_walk's iteration restated: the fill and resolve order of gm_walk.inc with NS = 2 slots.
-struct SlotWalk {
-  const DevIndex& ix;
-  const bool rp_on, ks_on;
-  std::vector<uint64_t> toks;
-  uint32_t n = 0;
-  bool dollar = false;
-  std::vector<uint32_t> out;
-  std::vector<std::pair<uint32_t, uint32_t>> stk;  // (node | item kind, level)
-  uint64_t loads = 0, iters = 0, rp_hits = 0, shared = 0;
-  static constexpr uint32_t IT_PLUS = 0x80000000u, IT_TN = 0x40000000u;
-  static constexpr uint32_t IT_KEYED = IT_PLUS | IT_TN, IT_KIND = IT_PLUS | IT_TN;
-  struct Slot {
-    bool busy = false, side = false;
-    uint32_t cur = 0, k = 0;
-    uint64_t key = 0, ia = 0;
-  };
-
-  SlotWalk(const DevIndex& x, bool rp, bool ks) : ix(x), rp_on(rp), ks_on(ks) {}
-  void em(uint32_t v) {
-    if (v == NONE) return;
-    if (v & LIST_MULTI) {
-      const uint32_t i = v & ~LIST_MULTI, c = ix.multi[i];
-      for (uint32_t j = 0; j < c; ++j) out.push_back(ix.multi[i + 1 + j]);
-    } else {
-      out.push_back(v);
-    }
-  }
-  uint32_t strip(uint32_t cf, uint32_t d) const {
-    const uint32_t h = cf_depth_code(cf & ix.leafp_mask);
-    return (h != 0u && (int)(n - d) > (int)h) ? (cf & ~(CF_LIT | CF_PLUS)) : cf;
-  }
-  void visit(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t d, bool lit, uint32_t kind = 0) {
-    if (hf != NONE) em(hf);
-    if (d == n) {
-      if (cf & CF_TW) em(tw);
-      if (lit && (cf & CF_TN) && dollar && n == 1) stk.push_back({IT_TN | (cf & CF_ID_MASK), d});
-    } else if (cf & CF_LIT) {
-      stk.push_back({(cf & CF_ID_MASK) | kind, d});
-    }
-  }
-  // rp: 1 = the root's state, 2 = its fat half's (gm_walk.inc create RP)
-  void create(uint32_t cf, uint32_t hf, uint32_t tw, uint32_t sig, uint32_t pcf, uint32_t phf,
-              uint32_t d, bool plus_ok, bool lit, bool fat = false, const uint4* h = nullptr,
-              uint32_t rp = 0) {
-    const bool keyed = sig == 0u && (cf & CF_LIT);
-    cf = strip(cf, d);
-    const uint64_t wtok = d < REC_TOKS ? (d < n ? toks[d] : 0ull) : 0ull;
-    const bool fat_go = fat && (cf & CF_LIT) && d < n && d < REC_TOKS &&
-                        (uint32_t)wtok == h[0].x && (uint32_t)(wtok >> 32) == h[0].y;
-    if (fat || (!keyed && d < REC_TOKS && !(sig & sig_bit(wtok)))) cf &= ~CF_LIT;
-    pcf = strip(pcf, d + 1);
-    visit(cf, hf, tw, d, lit, keyed ? IT_KEYED : 0u);
-    if (fat_go)
-      create(h[0].w, h[1].x, h[1].y, h[0].z >> SIG_SHIFT, h[1].z, h[1].w, d + 1, true, true, false,
-             nullptr, rp == 1 ? 2u : 0u);
-    if (!plus_ok || d >= n || !(cf & CF_PLUS)) return;
-    const bool ptw = (pcf & CF_PTW) != 0;
-    if (d + 1 == n && (pcf & CF_TW) && !ptw) {
-      stk.push_back({IT_PLUS | (cf & CF_ID_MASK), d});
-      return;
-    }
-    const uint32_t rpz = rp_on ? ix.rp0.z : NONE;  // (launch_walk: the tune masks the copy)
-    const bool r = rp == 2 && (rpz & CF_ID_MASK) == (pcf & CF_ID_MASK) && (pcf & CF_LIT) && d + 1 < n;
-    if (r) pcf &= ~CF_LIT;
-    visit(pcf & ~CF_PTW, ptw ? NONE : phf, ptw ? phf : NONE, d + 1, false);
-    if (r && (uint32_t)toks[d + 1] == ix.rp0.x && (uint32_t)(toks[d + 1] >> 32) == ix.rp0.y) {
-      ++rp_hits;
-      create(ix.rp0.w, ix.rp1.x, ix.rp1.y, ix.rp0.z >> SIG_SHIFT, ix.rp1.z, ix.rp1.w, d + 2, true, true);
-    }
-    if (d + 1 < n && (pcf & CF_PLUS)) stk.push_back({IT_PLUS | (pcf & CF_ID_MASK), d + 1});
-  }
-  // one bucket against (node, key): 1 hit (s, fat, hh filled), 0 an empty slot, -1 full of others
-  int bucket(uint64_t b, uint32_t node, uint64_t key, uint4 s[2], bool& fat, uint4 hh[2]) const {
-    const uint4* q = ix.edges + SLOT_U4 * EBUCKET * b;
-    for (uint32_t j = 0; j < EBUCKET; ++j)
-      if ((q[SLOT_U4 * j].z & CF_ID_MASK) == node && q[SLOT_U4 * j].x == (uint32_t)key &&
-          q[SLOT_U4 * j].y == (uint32_t)(key >> 32)) {
-        s[0] = q[SLOT_U4 * j];
-        s[1] = q[SLOT_U4 * j + 1];
-        fat = j == 0 && (q[SLOT_U4].z & CF_ID_MASK) == FAT_ID;
-        if (fat) {
-          hh[0] = q[SLOT_U4];
-          hh[1] = q[SLOT_U4 + 1];
-        }
-        return 1;
-      }
-    return (q[0].z == NONE || q[SLOT_U4].z == NONE) ? 0 : -1;
-  }
-  std::vector<uint32_t> run(const std::string& topic, uint64_t test_mask) {
-    std::vector<uint8_t> pl, hs;
-    bool hashed;
-    tokenize((const uint8_t*)topic.data(), (uint32_t)topic.size(), test_mask, toks, pl, hs, hashed);
-    n = (uint32_t)toks.size();
-    out.clear();
-    stk.clear();
-    for (size_t i = 0; i < n; ++i)
-      if (pl[i] || hs[i]) return out;
-    if (ix.trie_empty) return out;
-    dollar = !topic.empty() && topic[0] == '$';
-    const uint4 rh[2] = {ix.rh0, ix.rh1};
-    create(ix.root_cf, dollar ? NONE : ix.root_hf, NONE, ix.root_sig, ix.root_pcf, ix.root_phf, 0,
-           !dollar, false, (ix.rh0.z & CF_ID_MASK) == FAT_ID, rh, 1);
-    Slot P[2];
-    while (!stk.empty() || P[0].busy || P[1].busy) {
-      ++iters;
-      CHECK(iters < 100000, "topic '%s': the walk does not end", topic.c_str());
-      // ---- fill ----
-      uint32_t shk = NONE;
-      bool stop = false;
-      for (uint32_t j = 0; j < 2; ++j) {
-        Slot& p = P[j];
-        if (p.busy || stk.empty() || stop) continue;
-        if (j > 0 && shk != NONE && (stk.back().first & IT_KIND) == IT_KEYED && stk.back().second == shk) {
-          stop = true;  // a keyed sibling of slot 0's probe stays on the stack
-          continue;
-        }
-        const auto it = stk.back();
-        stk.pop_back();
-        const uint32_t kind = it.first & IT_KIND;
-        p.busy = true;
-        p.cur = it.first;
-        p.k = it.second;
-        p.side = kind == IT_TN || (kind != IT_PLUS && it.second >= REC_TOKS);
-        if (kind == IT_PLUS) p.key = PLUS_TOK;
-        else if (kind != IT_TN) p.key = toks[it.second];
-        if (j == 0 && ks_on && kind == IT_KEYED && it.second < REC_TOKS) shk = it.second;
-        if (!p.side) p.ia = edge_home(it.first & CF_ID_MASK, p.key, ix.emask, kind == IT_KEYED);
-      }
-      const size_t sh_lo = (shk != NONE && !stk.empty()) ? stk.size() - 1 : stk.size();
-      const uint64_t line0 = P[0].ia;  // slot 0's line of this round trip
-      for (uint32_t j = 0; j < 2; ++j) loads += P[j].busy && !P[j].side;
-      // ---- resolve ----
-      for (uint32_t j = 0; j < 2; ++j) {
-        Slot& p = P[j];
-        if (!p.busy) continue;
-        if (p.side) {
-          p.side = false;
-          if ((p.cur & IT_KIND) == IT_TN) {
-            p.busy = false;
-            em(ix.tn_of[p.cur & CF_ID_MASK]);
-          } else {
-            p.ia = edge_home(p.cur & CF_ID_MASK, p.key, ix.emask, (p.cur & IT_KIND) == IT_KEYED);
-          }
-          continue;
-        }
-        uint4 s[2], hh[2];
-        bool fat = false;
-        const int r = bucket(p.ia, p.cur & CF_ID_MASK, p.key, s, fat, hh);
-        if (r == 1) {
-          p.busy = false;
-          create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, p.k + 1, true,
-                 (p.cur & IT_KIND) != IT_PLUS, fat, hh);
-        } else if (r == 0) {
-          p.busy = false;
-        } else {
-          p.ia = (p.ia + 1) & ix.emask;
-        }
-      }
-      // ---- the late match: the first keyed item of slot 0's level against slot 0's line ----
-      if (shk != NONE) {
-        for (size_t i = sh_lo; i < stk.size(); ++i) {
-          if ((stk[i].first & IT_KIND) != IT_KEYED || stk[i].second != shk) continue;
-          const uint32_t node = stk[i].first & CF_ID_MASK;
-          CHECK(edge_home(node, toks[shk], ix.emask, true) == line0, "keyed siblings, two homes");
-          uint4 s[2], hh[2];
-          bool fat = false;
-          const int r = bucket(line0, node, toks[shk], s, fat, hh);
-          if (r != -1) {
-            ++shared;
-            stk[i] = stk.back();
-            stk.pop_back();
-          }
-          if (r == 1)
-            create(s[0].w, s[1].x, s[1].y, s[0].z >> SIG_SHIFT, s[1].z, s[1].w, shk + 1, true, true, fat, hh);
-          break;
-        }
-      }
-    }
-    return out;
-  }
-};
-
-struct Rig {
-  emqxgm_t* h = nullptr;
-  Oracle orc;
-  std::vector<std::string> topics;
-  uint32_t hash_bits = 0;
-  int fat = 1;
-
-  Rig(uint32_t hb, int keyed_mode, int fat_mode) : hash_bits(hb), fat(fat_mode) {
-    emqxgm_cfg cfg{};
-    cfg.word_hash_bits = hb;
-    CHECK(emqxgm_create(&cfg, &h) == 0, "create");
-    CHECK(emqxgm_tune(h, "keyed", keyed_mode) == 0, "tune keyed");
-    CHECK(emqxgm_tune(h, "fat_buckets", fat) == 0, "tune fat");
-    CHECK(emqxgm_tune(h, "delta_commit", 2) == 0, "tune delta");
-    // the new keys: accepted values, rejected values
+struct Rig : RigBase {
+  Rig(uint32_t hb, int keyed_mode, int fat_mode) : RigBase(hb, keyed_mode, fat_mode) {
+    // the rules' tune keys: accepted values, rejected values
     CHECK(emqxgm_tune(h, "root_plus_half", 0) == 0 && emqxgm_tune(h, "root_plus_half", 1) == 0 &&
               emqxgm_tune(h, "root_plus_half", 2) != 0, "tune root_plus_half");
     CHECK(emqxgm_tune(h, "keyed_share", 0) == 0 && emqxgm_tune(h, "keyed_share", 1) == 0 &&
               emqxgm_tune(h, "keyed_share", -1) != 0, "tune keyed_share");
-  }
-  ~Rig() {
-    g_deltas += deltas();
-    emqxgm_destroy(h);
-  }
-  void add(const std::string& f) {
-    CHECK(emqxgm_trie_insert(h, (const uint8_t*)f.data(), (uint32_t)f.size(), nullptr) == 0, "ins");
-    orc.add(f, 1);
-  }
-  void del(const std::string& f) {
-    CHECK(emqxgm_trie_delete(h, (const uint8_t*)f.data(), (uint32_t)f.size()) == 0, "del");
-    ref_trie_delete(orc.r, (const uint8_t*)f.data(), (uint32_t)f.size());
-  }
-  uint64_t deltas() {
-    emqxgm_stats st{};
-    emqxgm_get_stats(h, &st);
-    return st.delta_commits;
   }
 
   // want: 1 the copy must be there, 0 it must be absent, -1 either (absent is always correct)
@@ -273,66 +62,35 @@ struct Rig {
     }
   }
 
-  void rows(const char* what) {
-    std::string tb;
-    std::vector<uint32_t> toff(1, 0);
-    for (const auto& t : topics) {
-      tb += t;
-      toff.push_back((uint32_t)tb.size());
-    }
-    std::vector<uint64_t> row(topics.size() + 1);
-    std::vector<uint32_t> rex(topics.size());
-    uint32_t* ids = nullptr;
-    uint64_t nids = 0;
-    ref_match_batch(orc.r, (const uint8_t*)tb.data(), toff.data(), topics.size(), 1, row.data(), &ids,
-                    &nids, rex.data());
-    const DevIndex& ix = h->cur->ix;
-    for (size_t i = 0; i < topics.size(); ++i) {
-      CpuWalk w(ix);
-      std::vector<uint32_t> base = w.run(topics[i], h->test_mask);
-      std::sort(base.begin(), base.end());
-      for (int mode = 0; mode < 4; ++mode) {
-        SlotWalk sw(ix, (mode & 1) != 0, (mode & 2) != 0);
-        std::vector<uint32_t> got = sw.run(topics[i], h->test_mask);
-        std::sort(got.begin(), got.end());
-        CHECK(got == base, "%s: topic '%s': rules %d: %zu ids, the plain reader %zu", what,
-              topics[i].c_str(), mode, got.size(), base.size());
-        if (mode == 0 || mode == 3) {
-          g_loads[mode == 3] += sw.loads;
-          g_iters[mode == 3] += sw.iters;
-        }
-        if (mode == 3) {
-          g_rp_hits += sw.rp_hits;
-          g_shared += sw.shared;
-        }
+  // The restated walk with its two rules on and off, one at a time and together.  Lent
+  // signatures and closed buckets stay off in all four: mode 0 stands for production with tune
+  // "plus_sig" 0, "closed_buckets" 0, "root_plus_half" 0, "keyed_share" 0, mode 3 for the same
+  // with the last two at 1 -- so the loads and iterations compared are these two rules' alone.
+  void walks(const char* what, const std::string& topic, const std::vector<uint32_t>& base) {
+    for (int mode = 0; mode < 4; ++mode) {
+      WalkRules rules(h->cur->ix);
+      rules.lent = rules.cb = false;
+      rules.rp = (mode & 1) != 0;
+      rules.ks = (mode & 2) != 0;
+      const SlotWalk sw = slot_walk(rules, what, topic, base, ("rules " + S(mode)).c_str());
+      if (mode == 0 || mode == 3) {
+        g_loads[mode == 3] += sw.loads;
+        g_iters[mode == 3] += sw.iters;
       }
-      std::vector<std::string> gs, ws;
-      for (uint32_t f : base) {
-        const bool verify = (ix.fvbits[f >> 5] >> (f & 31)) & 1u;
-        const std::string fs = filter_str(h, f);
-        if (!verify || mqtt_match(topics[i], fs)) gs.push_back(fs);
+      if (mode == 3) {
+        g_rp_hits += sw.rp_hits;
+        g_shared += sw.shared;
       }
-      for (uint64_t j = row[i]; j < row[i + 1]; ++j) ws.push_back(orc.names[ids[j]]);
-      std::sort(gs.begin(), gs.end());
-      std::sort(ws.begin(), ws.end());
-      CHECK(gs == ws, "%s: topic '%s': %zu vs %zu filters", what, topics[i].c_str(), gs.size(), ws.size());
-      ++g_rows;
     }
-    ref_free(ids);
   }
 
   void step(const char* what, int want, bool delta = true) {
     if (!fat && want == 1) want = 0;  // without fat buckets the root has no half, so no copy
-    const uint64_t d0 = deltas();
-    CHECK(emqxgm_commit(h, nullptr) == 0, "%s: commit: %s", what, h->err.c_str());
-    ++g_commits;
-    if (delta && hash_bits == 0) CHECK(deltas() == d0 + 1, "%s: not a delta commit", what);
+    commit(what, delta);
     copy(what, want);
-    rows(what);
+    rows(what, [&](const std::string& t, const std::vector<uint32_t>& base) { walks(what, t, base); });
   }
 };
-
-std::string S(uint64_t v) { return std::to_string(v); }
 
 // A cfg3-shaped trie (4 sites x 8 devices, its five patterns): G = site, p = site/+, H =
 // site/+/device, and the churn of H's slot and of p's literal children.

@@ -9,44 +9,21 @@ deletes, re-inserts into TOMB slots, a fat half moving out, a node gaining and l
 child while its bucket is closed, a background full build with catch-up, a snapshot save and load
 with further deltas.  After every commit no live edge lies past a marked bucket on its own chain,
 marks sit only on live slots without a '+' child, model and table agree slot by slot, and the rows
-of the unchanged reader (harness_walk.h), of a restatement of k_walk's iteration with the rule on
-and off, and of the oracle are equal."""
-import os
+of the plain reader (harness_walk.h CpuWalk), of the restatement of k_walk's iteration (SlotWalk)
+with the rule on and off, and of the oracle are equal."""
 import subprocess
 
 import pytest
 
 import closed_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = os.path.join(ROOT, "tests", "host_harness")
-OUT = os.path.join(H, "build", "closed_harness_asan")
-SRCS = [os.path.join(H, "closed_harness.cpp"), os.path.join(H, "fake_hip.cpp"),
-        os.path.join(ROOT, "oracle", "ref_trie.cpp")]
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-DEPS = SRCS + [os.path.join(H, "fakehip", "hip", "hip_runtime.h"), os.path.join(H, "harness_walk.h")] + [
-    os.path.join(ROOT, "emqx_amd", "csrc", f) for f in ("gm_engine.cpp", "gm_common.h", "gm_kernels.h")
-] + [os.path.join(ROOT, "include", "emqx_gpumatch.h")]
-
-
-def _build():
-    if os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in DEPS):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-Wno-subobject-linkage",
-           "-I", os.path.join(H, "fakehip")] + SRCS + ["-pthread", "-o", OUT]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return OUT
+import host_build
 
 
 @pytest.mark.timeout(600)
 def test_closed_buckets_under_asan_ubsan():
-    exe = _build()
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=ENV,
-                       timeout=540)
+    exe = host_build.build("closed_harness.cpp")
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       env=host_build.ENV, timeout=540)
     assert r.returncode == 0, r.stdout[-6000:]
     last = r.stdout.strip().splitlines()[-1].split()
     assert last[0] == "OK", r.stdout[-2000:]
@@ -62,13 +39,13 @@ def test_census_of_the_miniature_restated(tmp_path):
     """The restated walk's bucket loads and lane iterations on the miniature cfg3 that
     tests/test_gpu_closed.py runs on the device: with the rule off the figures recorded for the
     parent's census on the device, with it on the figures the device census must equal."""
-    exe = _build()
+    exe = host_build.build("closed_harness.cpp")
     filters, topics = closed_cases.miniature()
     ff, tf = tmp_path / "filters.txt", tmp_path / "topics.txt"
     ff.write_text("".join(f + "\n" for f in filters))
     tf.write_text("".join(t + "\n" for t in topics))
     r = subprocess.run([exe, "--count", str(ff), str(tf)], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, env=ENV, timeout=540)
+                       stderr=subprocess.STDOUT, text=True, env=host_build.ENV, timeout=540)
     assert r.returncode == 0, r.stdout[-6000:]
     last = r.stdout.strip().splitlines()[-1].split()
     assert last[0] == "COUNT", r.stdout[-2000:]

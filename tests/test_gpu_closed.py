@@ -16,7 +16,7 @@ import random
 import pytest
 
 import closed_cases
-from oracle import emqx_ref as R
+import walk_rule_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -32,66 +32,18 @@ def emqx():
 
 
 def _load(emqx, filters, bits=0, keyed=2):
-    eng = emqx.Engine(word_hash_bits=bits)
-    eng.tune("keyed", keyed)
-    eng.tune("delta_commit", 2)  # patch whenever possible
-    py = R.Trie()
-    for f in filters:
-        f = f if isinstance(f, bytes) else f.encode()
-        eng.trie_insert(f)
-        py.insert(f)
-    eng.commit()
-    return eng, py
-
-
-def _reset(eng):
-    for k in ("walk_pair", "root_plus_half", "keyed_share", "closed_buckets"):
-        eng.tune(k, 1)
+    return W.load(emqx, filters, bits=bits, keyed=keyed)
 
 
 def _check(eng, py, topics, what="", pairs=(0, 1, 2)):
-    topics = [t if isinstance(t, bytes) else t.encode() for t in topics]
-    want = [sorted(py.match(t)) for t in topics]  # (once per state, shared by the matrix)
-    names = {}
-
-    def name(f):
-        if f not in names:
-            names[f] = eng.filter_bytes(f)
-        return names[f]
-
-    for pair in pairs:
-        eng.tune("walk_pair", pair)
-        for cb in (1, 0):
-            eng.tune("closed_buckets", cb)
-            for rp in (1, 0):
-                eng.tune("root_plus_half", rp)
-                for ks in (1, 0):
-                    eng.tune("keyed_share", ks)
-                    res = eng.match(topics)
-                    for i, t in enumerate(topics):
-                        got = sorted(name(int(f)) for f in res.row(i))
-                        assert got == want[i], (what, pair, cb, rp, ks, t)
-    _reset(eng)
-    return want
-
-
-def _census(eng, topics):
-    import numpy as np
-    import torch
-    from emqx_amd.engine import pack
-    topics = [t if isinstance(t, bytes) else t.encode() for t in topics]
-    tb, to = pack(topics, np.uint32)
-    db = torch.from_numpy(tb).cuda()
-    do = torch.from_numpy(to.view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return eng.walk_census(db.data_ptr(), do.data_ptr(), len(topics), int(to[-1]))
+    return W.check(eng, py, topics, what, ("closed_buckets", "root_plus_half", "keyed_share"), pairs)
 
 
 def _census_both(eng, topics):
     c = {}
     for cb in (0, 1):
         eng.tune("closed_buckets", cb)
-        c[cb] = _census(eng, topics)
+        c[cb] = W.census(eng, topics)
     eng.tune("closed_buckets", 1)
     return c
 

@@ -13,7 +13,7 @@ import random
 
 import pytest
 
-from oracle import emqx_ref as R
+import walk_rule_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -26,43 +26,12 @@ def emqx():
     return emqx_amd
 
 
-def _load(emqx, filters, bits=0, keyed=2):
-    eng = emqx.Engine(word_hash_bits=bits)
-    eng.tune("keyed", keyed)
-    eng.tune("delta_commit", 2)  # patch whenever possible
-    py = R.Trie()
-    for f in sorted(set(filters)):
-        f = f if isinstance(f, bytes) else f.encode()
-        eng.trie_insert(f)
-        py.insert(f)
-    eng.commit()
-    return eng, py
+def _load(emqx, filters, bits=0):
+    return W.load(emqx, filters, bits=bits, keyed=2, dedup_sorted=True)
 
 
 def _check(eng, py, topics, what=""):
-    topics = [t if isinstance(t, bytes) else t.encode() for t in topics]
-    want = [sorted(py.match(t)) for t in topics]  # (once per state, shared by the matrix)
-    names = {}
-
-    def name(f):
-        if f not in names:
-            names[f] = eng.filter_bytes(f)
-        return names[f]
-
-    for pair in (0, 1, 2):
-        eng.tune("walk_pair", pair)
-        for rp in (1, 0):
-            eng.tune("root_plus_half", rp)
-            for ks in (1, 0):
-                eng.tune("keyed_share", ks)
-                res = eng.match(topics)
-                for i, t in enumerate(topics):
-                    got = sorted(name(int(f)) for f in res.row(i))
-                    assert got == want[i], (what, pair, rp, ks, t)
-    eng.tune("walk_pair", 1)
-    eng.tune("root_plus_half", 1)
-    eng.tune("keyed_share", 1)
-    return want
+    return W.check(eng, py, topics, what, ("root_plus_half", "keyed_share"))
 
 
 def _step(eng, py, topics, what, add=(), delete=()):
@@ -74,17 +43,6 @@ def _step(eng, py, topics, what, add=(), delete=()):
         py.insert(f.encode())
     eng.commit()
     return _check(eng, py, topics, what)
-
-
-def _census(eng, topics):
-    import numpy as np
-    import torch
-    from emqx_amd.engine import pack
-    tb, to = pack(topics, np.uint32)
-    db = torch.from_numpy(tb).cuda()
-    do = torch.from_numpy(to.view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return eng.walk_census(db.data_ptr(), do.data_ptr(), len(topics), int(to[-1]))
 
 
 SITES, DEVS = 8, 24
@@ -149,7 +107,7 @@ def test_miniature_cfg3(emqx, bits):
             for ks in (0, 1):
                 eng.tune("root_plus_half", rp)
                 eng.tune("keyed_share", ks)
-                c[rp, ks] = _census(eng, [t.encode() for t in topics])
+                c[rp, ks] = W.census(eng, topics)
         eng.tune("root_plus_half", 1)
         eng.tune("keyed_share", 1)
         print({k: (v["slot_loads"], v["lane_iters"]) for k, v in c.items()})

@@ -17,10 +17,9 @@ which must be unaffected by the lent bits in the slots it reads).
 A last case runs a topic whose rank passes the packed staging's rank field."""
 import random
 
-import numpy as np
 import pytest
 
-from oracle import emqx_ref as R
+import walk_rule_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -85,48 +84,16 @@ def _topics():
 def _check(eng, py, topics, what=""):
     """Rows equal the oracle's with the rule on and off, through the one-lane walk (walk_pair 0:
     the kernel with the filter), the default choice (1) and the pair walk (2)."""
-    want = [sorted(py.match(t)) for t in topics]
-    names = {}
-
-    def name(f):
-        if f not in names:
-            names[f] = eng.filter_bytes(f)
-        return names[f]
-
-    for pair in (0, 1, 2):
-        eng.tune("walk_pair", pair)
-        for on in (1, 0):
-            eng.tune("plus_sig", on)
-            res = eng.match(topics)
-            for i, t in enumerate(topics):
-                got = sorted(name(int(f)) for f in res.row(i))
-                assert got == want[i], (what, pair, on, t)
-    eng.tune("plus_sig", 1)
-    eng.tune("walk_pair", 1)
+    W.check(eng, py, topics, what, ("plus_sig",))
 
 
 def _load(emqx, filters, bits=0, keyed=1, fat=1):
-    eng = emqx.Engine(word_hash_bits=bits)
-    eng.tune("keyed", keyed)
-    eng.tune("fat_buckets", fat)
-    eng.tune("delta_commit", 2)  # patch whenever possible
-    py = R.Trie()
-    for f in filters:
-        eng.trie_insert(f)
-        py.insert(f)
-    eng.commit()
-    return eng, py
+    return W.load(emqx, filters, bits=bits, keyed=keyed, fat=fat)
 
 
 def _level5(eng, topics):
     """Literal probes of level 5 (the k of site/S/device/D/m/k) of one census pass."""
-    import torch
-    from emqx_amd.engine import pack
-    tb, to = pack(topics, np.uint32)
-    db = torch.from_numpy(tb).cuda()
-    do = torch.from_numpy(to.view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return eng.walk_census(db.data_ptr(), do.data_ptr(), len(topics), int(to[-1]))["loads_by_level"]["literal"][5]
+    return W.census(eng, topics)["loads_by_level"]["literal"][5]
 
 
 @pytest.mark.parametrize("fat", [1, 0])

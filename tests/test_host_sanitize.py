@@ -16,39 +16,11 @@ emqxgm_route_set_batch(.., EMQXGM_SET_COMMIT) during a bulk commit's build, duri
 tables' load started, and a batch too large for a delta during a build -- each checked on the
 epoch readers have right after the call (the reference's subscriber has its route before SUBACK,
 emqx_broker.erl:163-168, emqx_router.erl:124-138) -- under ThreadSanitizer and ASan + UBSan."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = os.path.join(ROOT, "tests", "host_harness")
-OUT = os.path.join(H, "build", "harness_asan")
-SRCS = [os.path.join(H, "harness.cpp"), os.path.join(H, "fake_hip.cpp"),
-        os.path.join(ROOT, "oracle", "ref_trie.cpp")]
-DEPS = SRCS + [os.path.join(H, "fakehip", "hip", "hip_runtime.h"), os.path.join(H, "harness_walk.h")] + [
-    os.path.join(ROOT, "emqx_amd", "csrc", f) for f in ("gm_engine.cpp", "gm_common.h", "gm_kernels.h")
-] + [os.path.join(ROOT, "include", "emqx_gpumatch.h")]
-
-
-SAN = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                "-fno-omit-frame-pointer"],
-       "tsan": ["-fsanitize=thread"]}
-
-
-def _build(main="harness.cpp", san="asan"):
-    out = OUT if (main, san) == ("harness.cpp", "asan") else os.path.join(
-        H, "build", main.replace(".cpp", "") + "_" + san)
-    srcs = [os.path.join(H, main)] + SRCS[1:]
-    deps = DEPS + [srcs[0]]
-    if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = ["g++", "-std=c++17", "-O1", "-g"] + SAN[san] + [
-        "-Wno-subobject-linkage", "-I", os.path.join(H, "fakehip")] + srcs + ["-pthread", "-o", out]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return out
+import host_build
 
 
 @pytest.mark.timeout(600)
@@ -57,12 +29,10 @@ def _build(main="harness.cpp", san="asan"):
 def test_engine_host_code_under_asan_ubsan(seed, rounds, hash_bits, keyed, tmp_path):
     """keyed 2: every eligible trie node token-keyed (gm_common.h edge_home), so the CPU walk
     and the delta commits run over keyed placements."""
-    exe = _build()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = host_build.build("harness.cpp")
     r = subprocess.run([exe, str(seed), str(rounds), str(hash_bits), str(tmp_path), str(keyed)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env,
-                       timeout=540)
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       env=host_build.ENV, timeout=540)
     assert r.returncode == 0, r.stdout[-6000:]
     last = r.stdout.strip().splitlines()[-1].split()
     assert last[0] == "OK", r.stdout[-2000:]
@@ -82,12 +52,9 @@ def test_subscribe_visible_during_background_builds(san, seed, delta_max):
     builds (fake HIP runtime: host-side cost only).  delta_max: the changes a delta takes
     (tune "delta_max"; 0 = the default bound, 4096 at these sizes) -- small under TSan to keep
     the bulk small."""
-    exe = _build("bg_harness.cpp", san)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
-               TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
+    exe = host_build.build("bg_harness.cpp", san)
     r = subprocess.run([exe, str(seed), str(delta_max)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, env=env, timeout=840)
+                       text=True, env=host_build.ENV, timeout=840)
     assert r.returncode == 0, r.stdout[-6000:]
     last = r.stdout.strip().splitlines()[-1].split()
     assert last[0] == "OK", r.stdout[-2000:]

@@ -11,41 +11,19 @@ After the full build and after every step every live slot of the committed table
 CF_LIT clear and a carried '+' child the lent bits contain the class of every live literal child
 of that '+' node, with CF_LIT set the field is the node's own (or the keyed 0), and every slot
 equals what the model gives for its node.  The rows of the CPU walk that ignores lent bits
-(harness_walk.h, unchanged) stay equal to the oracle's."""
-import os
+(harness_walk.h CpuWalk) stay equal to the oracle's."""
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = os.path.join(ROOT, "tests", "host_harness")
-OUT = os.path.join(H, "build", "psig_harness_asan")
-SRCS = [os.path.join(H, "psig_harness.cpp"), os.path.join(H, "fake_hip.cpp"),
-        os.path.join(ROOT, "oracle", "ref_trie.cpp")]
-DEPS = SRCS + [os.path.join(H, "fakehip", "hip", "hip_runtime.h"), os.path.join(H, "harness_walk.h")] + [
-    os.path.join(ROOT, "emqx_amd", "csrc", f) for f in ("gm_engine.cpp", "gm_common.h", "gm_kernels.h")
-] + [os.path.join(ROOT, "include", "emqx_gpumatch.h")]
-
-
-def _build():
-    if os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in DEPS):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-Wno-subobject-linkage",
-           "-I", os.path.join(H, "fakehip")] + SRCS + ["-pthread", "-o", OUT]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return OUT
+import host_build
 
 
 @pytest.mark.timeout(600)
 def test_lent_signature_invariant_under_asan_ubsan():
-    exe = _build()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env,
-                       timeout=540)
+    exe = host_build.build("psig_harness.cpp")
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       env=host_build.ENV, timeout=540)
     assert r.returncode == 0, r.stdout[-6000:]
     last = r.stdout.strip().splitlines()[-1].split()
     assert last[0] == "OK", r.stdout[-2000:]
