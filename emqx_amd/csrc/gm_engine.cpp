@@ -2849,7 +2849,9 @@ int ensure_input(emqxgm* h, uint64_t bytes, uint64_t offs) {
   if (bytes > h->in_bytes_cap) {
     if (h->d_in_bytes) (void)hipFree(h->d_in_bytes);
     h->d_in_bytes = nullptr;
-    const uint64_t cap = std::max<uint64_t>(bytes, 1 << 20);
+    // whole 16-B chunks: k_tok and k_exact stage a tile with 16-B loads, the last one of a batch
+    // reaching up to 15 bytes past its end (gm_tok.inc stage_tile)
+    const uint64_t cap = (std::max<uint64_t>(bytes, 1 << 20) + 15) & ~15ull;
     HIPCHK(h, hipMalloc((void**)&h->d_in_bytes, cap));
     h->in_bytes_cap = cap;
   }
@@ -2901,7 +2903,9 @@ int host_pipe_reserve(emqxgm* h, emqxgm::HostPipe& p, uint64_t n, uint64_t bytes
     if (p.d_bytes) (void)hipFree(p.d_bytes);
     p.d_bytes = nullptr;
     p.bytes_cap = 0;
-    const uint64_t cap = std::max<uint64_t>(bytes + bytes / 4, 1 << 20);
+    // whole 16-B chunks, as in ensure_input: a later window that ends in the capacity's last
+    // chunk does not regrow it, and the copy-through k_tok also stores the chunks it read
+    const uint64_t cap = (std::max<uint64_t>(bytes + bytes / 4, 1 << 20) + 15) & ~15ull;
     HIPCHK(h, hipMalloc((void**)&p.d_bytes, cap));
     p.bytes_cap = cap;
   }
@@ -4684,8 +4688,10 @@ int emqxgm_match_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offset
 void* emqxgm_host_alloc(emqxgm_t* h, uint64_t bytes) {
   if (!h) return nullptr;
   void* p = nullptr;
+  // whole 16-B chunks: a window of topic bytes that fills the buffer is read by the copy-through
+  // k_tok in 16-B loads (emqxgm_match_batch_submit_filters), the last one up to 15 bytes past it
   if (hipSetDevice(h->cfg.device) != hipSuccess ||
-      hipHostMalloc(&p, std::max<uint64_t>(bytes, 1), hipHostMallocPortable) != hipSuccess)
+      hipHostMalloc(&p, (std::max<uint64_t>(bytes, 1) + 15) & ~15ull, hipHostMallocPortable) != hipSuccess)
     return nullptr;
   return p;
 }

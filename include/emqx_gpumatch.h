@@ -249,7 +249,13 @@ int emqxgm_filters_copy(emqxgm_t* h, const uint32_t* ids, uint64_t n, uint8_t* b
 int emqxgm_match_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
                        emqxgm_out* out);
 /* Same, with bytes/offsets already in HBM on the handle's device; results stay in HBM.
- * bytes_len = offsets[n] (passed so the engine never has to read it back). */
+ * bytes_len = offsets[n] (passed so the engine never has to read it back).
+ * The kernels read the batch in aligned 16-byte chunks: the chunks that hold its first and its
+ * last byte are read whole, so up to 15 bytes in front of d_bytes and behind d_bytes + bytes_len
+ * (never a chunk that holds no byte of the batch) must be readable device memory; their values
+ * do not matter.  A batch anywhere inside an allocation whose start and size are multiples of
+ * 16 bytes satisfies this.  The same holds for emqxgm_match_device_submit and
+ * emqxgm_exact_owned_device (aligned 4-byte words there). */
 int emqxgm_match_device(emqxgm_t* h, const uint8_t* d_bytes, const uint32_t* d_offsets,
                         uint32_t n, uint64_t bytes_len, emqxgm_dev_out* out);
 
@@ -272,7 +278,8 @@ int emqxgm_device_pipes(void);
 
 /* Pinned (page-locked) host memory on the handle's device, for the caller's topic staging: a
  * batcher that packs its window into it gets full-speed H2D copies from emqxgm_match_batch.
- * NULL on failure.  emqxgm_host_free releases it. */
+ * The size is rounded up to a multiple of 16 bytes.  NULL on failure.  emqxgm_host_free
+ * releases it. */
 void* emqxgm_host_alloc(emqxgm_t* h, uint64_t bytes);
 void emqxgm_host_free(emqxgm_t* h, void* p);
 int emqxgm_match_device_submit(emqxgm_t* h, const uint8_t* d_bytes, const uint32_t* d_offsets,
@@ -320,7 +327,10 @@ int emqxgm_match_batch_wait_filters(emqxgm_t* h, uint64_t ticket, emqxgm_batch_o
  * (emqxgm_tune; 65536 default) and 8 MiB whose bytes and offsets are pinned memory
  * (emqxgm_host_alloc) goes without DMA copies: the tokenizer reads it over PCIe and the result
  * block is written straight into the pipe's pinned buffer (r04: 16k-topic windows 150 -> 114 us
- * one at a time).  Either way bytes / offsets stay untouched until the wait. */
+ * one at a time).  Either way bytes / offsets stay untouched until the wait.  Such a window
+ * (bytes 16-byte aligned, or it takes the copies) is read in whole 16-byte chunks, up to 15 bytes
+ * past bytes + offsets[n]: those bytes must be part of the pinned buffer.  emqxgm_host_alloc
+ * rounds its size up to a multiple of 16, so a window that fills its buffer satisfies this. */
 int emqxgm_match_batch_submit_filters(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offsets,
                                       uint32_t n, uint64_t* ticket);
 

@@ -22,12 +22,13 @@ DEPS = LINKED + [os.path.join(ROOT, "include", "emqx_gpumatch.h")] + [
                                     "gm_roctx.h")]
 
 
-def build(main, san="asan"):
+def build(main, san="asan", deps=()):
     """tests/host_harness/<main> -> tests/host_harness/build/<main without .cpp>_<san>, rebuilt
-    when a source or header it is made of is newer."""
+    when a source or header it is made of (deps: what this program includes beyond DEPS) is
+    newer."""
     src = os.path.join(H, main)
     out = os.path.join(H, "build", main.replace(".cpp", "") + "_" + san)
-    if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in DEPS + [src]):
+    if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in DEPS + [src] + list(deps)):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = ["g++", "-std=c++17", "-O1", "-g"] + SAN[san] + [

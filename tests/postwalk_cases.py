@@ -52,6 +52,37 @@ def word_token_bits(word: bytes, bits: int) -> int:
     return h & ((1 << bits) - 1)
 
 
+def word_token(word: bytes) -> int:
+    """word_token (gm_common.h) in production mode: a word of at most TOK_INLINE_MAX = 7 bytes is
+    its bytes little-endian in bits 0..55 and its length in bits 56..62; a longer one is bit 63
+    and fmix64 of its FNV-1a state, shifted right by one."""
+    if len(word) <= 7:
+        return int.from_bytes(word, "little") | (len(word) << 56)
+    return (1 << 63) | (word_token_bits(word, 64) >> 1)
+
+
+def _fmix64(k: int) -> int:
+    k ^= k >> 33
+    k = (k * 0xff51afd7ed558ccd) & _M64
+    k ^= k >> 33
+    k = (k * 0xc4ceb9fe1a85ec53) & _M64
+    return k ^ (k >> 33)
+
+
+def key_hash(key: bytes, bits: int = 64) -> int:
+    """key_hash (gm_common.h): the key's bytes as little-endian dwords, the last zero-padded, in
+    two 32-bit multiply-rotate lanes folded through fmix64; the low `bits` bits are kept."""
+    m = 0xFFFFFFFF
+    a, b = 0x9747b28c ^ len(key), (0x85ebca6b + len(key)) & m
+    for i in range(0, len(key), 4):
+        w = int.from_bytes(key[i:i + 4], "little")
+        a ^= (w * 0xcc9e2d51) & m
+        a = ((((a << 15) | (a >> 17)) & m) * 5 + 0xe6546b64) & m
+        b = (b + w * 0x1b873593) & m
+        b = (((((b << 13) | (b >> 19)) & m) * 0x85ebca6b) & m) ^ 0xc2b2ae35
+    return _fmix64((a << 32) | b) & ((1 << bits) - 1)
+
+
 def filters():
     out = []
     for k in range(6):
