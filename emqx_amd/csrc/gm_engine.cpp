@@ -32,115 +32,12 @@
 #include "gm_common.h"
 #include "gm_internal.h"
 #include "gm_kernels.h"
+#include "gm_model.h"
 #include "gm_roctx.h"
 
 using namespace gm;
 
 namespace {
-
-uint64_t pow2_at_least(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
-// Open-addressing map (parent node, level token) -> child node (host-side trie; kept between
-// commits for delta commits, so it also erases: a freed entry becomes a TOMB that lookups pass).
-struct EdgeMap {
-  struct Ent {
-    uint64_t tok;
-    uint32_t parent;  // NONE = empty, TOMB = erased
-    uint32_t child;
-  };
-  std::vector<Ent> ents;
-  uint64_t mask = 0, used = 0;  // used counts erased entries too
-  void init(uint64_t expect) {
-    const uint64_t cap = pow2_at_least(std::max<uint64_t>(16, expect * 2));
-    ents.assign(cap, Ent{0, NONE, 0});
-    mask = cap - 1;
-    used = 0;
-  }
-  void grow() {
-    std::vector<Ent> old;
-    old.swap(ents);
-    ents.assign(old.size() * 2, Ent{0, NONE, 0});
-    mask = ents.size() - 1;
-    used = 0;
-    bool ins;
-    for (const Ent& e : old)
-      if (e.parent != NONE && e.parent != TOMB) *get_or_insert(e.parent, e.tok, ins) = e.child;
-  }
-  // returns pointer to the child slot; inserted=true if new
-  uint32_t* get_or_insert(uint32_t parent, uint64_t tok, bool& inserted) {
-    if ((used + 1) * 2 > mask + 1) grow();
-    uint64_t i = edge_slot(parent, tok, mask), free_at = ~0ull;
-    for (;;) {
-      Ent& e = ents[i];
-      if (e.parent == parent && e.tok == tok) {
-        inserted = false;
-        return &e.child;
-      }
-      if (e.parent == TOMB && free_at == ~0ull) free_at = i;
-      if (e.parent == NONE) {
-        if (free_at == ~0ull) {
-          free_at = i;
-          ++used;
-        }
-        Ent& f = ents[free_at];
-        f.parent = parent;
-        f.tok = tok;
-        inserted = true;
-        return &f.child;
-      }
-      i = (i + 1) & mask;
-    }
-  }
-  uint32_t* find(uint32_t parent, uint64_t tok) {
-    if (ents.empty()) return nullptr;
-    for (uint64_t i = edge_slot(parent, tok, mask);; i = (i + 1) & mask) {
-      Ent& e = ents[i];
-      if (e.parent == parent && e.tok == tok) return &e.child;
-      if (e.parent == NONE) return nullptr;
-    }
-  }
-  bool erase(uint32_t parent, uint64_t tok) {
-    uint32_t* c = find(parent, tok);
-    if (!c) return false;
-    Ent* e = (Ent*)((uint8_t*)c - offsetof(Ent, child));
-    e->parent = TOMB;
-    return true;
-  }
-};
-
-// Level tokens of a filter/topic string, exactly as the device tokenizer computes them.
-// is_plus/is_hash flag words that are exactly '+' / '#'; `hashed` = some literal word got a
-// hashed token (its trie pairs need byte verification).
-void tokenize(const uint8_t* p, uint32_t len, uint64_t test_mask, std::vector<uint64_t>& toks,
-              std::vector<uint8_t>& is_plus, std::vector<uint8_t>& is_hash, bool& hashed) {
-  toks.clear();
-  is_plus.clear();
-  is_hash.clear();
-  hashed = false;
-  uint32_t s = 0;
-  for (uint32_t i = 0; i <= len; ++i) {
-    if (i == len || p[i] == '/') {
-      const uint32_t wl = i - s;
-      uint64_t packed = 0, fnv = FNV_OFF;
-      for (uint32_t q = 0; q < wl; ++q) {
-        if (q < 8) packed |= (uint64_t)p[s + q] << (8 * q);
-        fnv = fnv_step(fnv, p[s + q]);
-      }
-      const bool pl = (wl == 1 && p[s] == '+');
-      const bool hs = (wl == 1 && p[s] == '#');
-      const uint64_t tok = word_token(packed, fnv, wl, test_mask);
-      toks.push_back(tok);
-      is_plus.push_back(pl);
-      is_hash.push_back(hs);
-      if (!pl && !hs && (tok & TOK_HASHED)) hashed = true;
-      s = i + 1;
-    }
-  }
-}
 
 struct Filter {
   uint64_t off;
@@ -223,9 +120,6 @@ struct PassCtx {
   const uint32_t* src_off = nullptr;
 };
 
-constexpr uint64_t DEAD = ~0ull;  // TrieModel::slot of the root and of removed nodes
-constexpr uint64_t ROOTH = ~1ull; // TrieModel::slot of the root's fat half (kernel arguments)
-
 // Device writes staged by one commit (k_patch): dword runs to device addresses, uploaded in
 // one copy and applied by one launch on the engine stream.
 struct PatchList {
@@ -246,200 +140,6 @@ struct PatchList {
   void clear() {
     ents.clear();
     src.clear();
-  }
-};
-
-// Host model of the committed trie and exact table, kept so that a commit with a small delta
-// patches the device tables in place (commit_delta) instead of rebuilding them.  A slot's 32 B
-// are a function of its node's state (node_slot), so only positions and occupancy are mirrored.
-struct TrieModel {
-  bool valid = false;  // false: the next commit is a full build
-  EdgeMap emap;
-  // per node (root = 0): hf/tw/tn are NONE, a filter id, or LIST_MULTI | multi[] position
-  std::vector<uint32_t> parent, ref, nlit, pchild, hf, tw, tn;
-  std::vector<uint8_t> sig;    // gm_common.h sig_bit classes of the node's literal children
-  std::vector<uint8_t> hcode;  // depth code (gm_common.h CF_H0/CF_H1): exact at a full build,
-                               // only reset to 0 (unbounded) by delta commits
-  std::vector<uint64_t> tok;
-  std::vector<uint64_t> slot;       // edge slot of the node's incoming edge (DEAD: root/removed,
-                                    // ROOTH: the root's fat half, carried in the arguments)
-  // fat buckets (gm_common.h FAT_ID): fchild = the node's only literal child when that child's
-  // slot is the second half of the node's bucket (the root's: the arguments), else 0; half = the
-  // node is such a child
-  std::vector<uint32_t> fchild;
-  std::vector<uint8_t> half;
-  std::vector<uint8_t> keyed;  // the node's children are placed by token (gm_common.h edge_home)
-  // the only literal child of a depth-2 '+' node (G/+ for a first-level node G), kept while that
-  // node has exactly one: set when its nlit becomes 1, dropped when it becomes 2 or a literal
-  // child goes (after a deletion back to one it stays absent until the next full build; absent
-  // is always correct).  Feeds root_plus_half; not part of a snapshot (lone_rebuild).
-  std::unordered_map<uint32_t, uint32_t> lone;
-  std::vector<uint64_t> occ, tomb;  // bitmaps over edge slots: used (live or TOMB), TOMB
-  // closed buckets (gm_common.h EDGE_CLOSED).  open: a bit per bucket, set when some edge whose
-  // chain passes the bucket was placed beyond it -- exact after a full build and a snapshot load
-  // (closed_rebuild), only ever set by delta commits (a deletion leaves it).  owner: the node of
-  // each slot's live edge (NONE: empty or TOMB), so that a delta commit that opens a bucket can
-  // re-emit the slots that carried its mark.  Neither is part of a snapshot.
-  std::vector<uint64_t> open;
-  std::vector<uint32_t> owner;
-  uint64_t nbk = 0, ecap = 0, n_occ = 0, n_edges = 0, tn_cap = 0, fv_cap = 0;
-  std::vector<uint32_t> fvbits;
-  std::vector<uint32_t> multi;  // [count, fid...] lists of nodes shared by several filters
-  bool needs_verify = false;
-  uint32_t max_depth = 0;
-  uint64_t n_trie = 0, n_route = 0;
-  uint64_t n_nodes0 = 0, fv_words0 = 0;  // nodes / verify words at the build (headroom used since)
-  // exact route keys: entry per committed key, bitmaps over entries.  Two regions of one
-  // table: plain (non-wildcard) keys in buckets [0, xcap_p), wildcard keys in [xcap_p,
-  // xcap_p + xcap_w); a name can only equal a key of its own kind (same bytes, same words).
-  std::vector<uint32_t> xpos;
-  std::vector<uint64_t> xocc, xtomb, xovf;  // xovf: a bit per bucket (gm_common.h)
-  uint64_t xcap_p = 0, xcap_w = 0, x_occ_p = 0, x_occ_w = 0, n_route_p = 0, n_route_w = 0;
-  uint64_t xbase(bool w) const { return w ? xcap_p : 0; }
-  uint64_t xcapr(bool w) const { return w ? xcap_w : xcap_p; }
-  uint64_t& xoccr(bool w) { return w ? x_occ_w : x_occ_p; }
-  uint64_t& nroute(bool w) { return w ? n_route_w : n_route_p; }
-  // home bucket of a key hash in its region, and the next bucket of its probe sequence
-  uint64_t xhome(bool w, uint64_t fh) const { return xbase(w) + exact_slot(fh, xcapr(w) - 1); }
-  uint64_t xnext(bool w, uint64_t b) const {
-    return xbase(w) + ((b - xbase(w) + 1) & (xcapr(w) - 1));
-  }
-  // device tables patched in place (owned by emqxgm::o_tab)
-  uint32_t *d_edges = nullptr, *d_exact = nullptr, *d_tn = nullptr, *d_fv = nullptr,
-           *d_xovf = nullptr;
-
-  uint32_t cf(uint32_t i) const {  // gm_common.h cf: id | flags
-    uint32_t f = i;
-    if (nlit[i]) f |= CF_LIT;
-    if (pchild[i]) f |= CF_PLUS;
-    if (tw[i] != NONE) f |= CF_TW;
-    if (tn[i] != NONE) f |= CF_TN;
-    return cf_with_depth_code(f, hcode[i]);
-  }
-  uint32_t hfd(uint32_t i) const { return hf[i]; }  // id, LIST_MULTI | multi index, or NONE
-  // The signature field of c's slot (gm_common.h "Child signature"): c's own literal children's
-  // classes, 0 for a keyed node with literal children (the keyed flag) -- and, when c has no
-  // literal child (CF_LIT clear, its own signature unused), the classes of the literal children
-  // of c's '+' child, lent to the walk (a keyed node that lost its last literal child lends
-  // them too: a 0 there would rule out every child of the '+' node).  A '+' node is never keyed.
-  uint32_t sig_field(uint32_t c) const {
-    if (nlit[c]) return keyed[c] ? 0u : (uint32_t)sig[c];
-    return pchild[c] ? (uint32_t)sig[pchild[c]] : 0u;
-  }
-  void node_slot(uint32_t c, uint4* sl) const {  // the 2 x uint4 of c's incoming edge
-    const uint32_t p = pchild[c];
-    sl[0] = make_uint4((uint32_t)tok[c], (uint32_t)(tok[c] >> 32),
-                       (half[c] ? FAT_ID : parent[c]) | (sig_field(c) << SIG_SHIFT), cf(c));
-    sl[1] = make_uint4(hfd(c), tw[c], p ? pcf(p) : 0u, p ? phf(p) : closed_mark(c));
-  }
-  // s1.w of a slot whose node has no '+' child: EDGE_CLOSED while its bucket is closed (the
-  // root's half, carried in the arguments, has no bucket)
-  uint32_t closed_mark(uint32_t c) const {
-    const uint64_t s = slot[c];
-    if (s == DEAD || s == ROOTH || (s / EBUCKET >> 6) >= open.size()) return NONE;
-    return (open[s / EBUCKET >> 6] >> (s / EBUCKET & 63)) & 1 ? NONE : EDGE_CLOSED;
-  }
-  // open and owner from the placement: every bucket from an edge's home up to its slot's is
-  // open (a fat half sits in its parent's bucket, on no chain of its own).  False: some slot is
-  // not on its edge's chain (a corrupt snapshot).
-  bool closed_rebuild() {
-    open.assign(nbk / 64 + 1, 0ull);
-    owner.assign(ecap, NONE);
-    for (uint32_t c = 1; c < parent.size(); ++c) {
-      if (slot[c] == DEAD || slot[c] == ROOTH) continue;
-      if (slot[c] >= ecap || owner[slot[c]] != NONE) return false;
-      owner[slot[c]] = c;
-      if (half[c]) continue;
-      uint64_t b = home(parent[c], tok[c]), steps = 0;
-      for (; b != slot[c] / EBUCKET; b = (b + 1) & (nbk - 1)) {
-        if (++steps >= nbk) return false;
-        open[b >> 6] |= 1ull << (b & 63);
-      }
-    }
-    return true;
-  }
-  // the carried copy of '+' child p (gm_common.h CF_PTW): its '#' filter, or -- when it has
-  // none -- its terminal filters, flagged
-  bool ptw(uint32_t p) const { return hf[p] == NONE && tw[p] != NONE; }
-  uint32_t pcf(uint32_t p) const { return cf(p) | (ptw(p) ? CF_PTW : 0u); }
-  uint32_t phf(uint32_t p) const { return ptw(p) ? tw[p] : hfd(p); }
-  uint32_t new_node(uint32_t par, uint64_t t) {
-    const uint32_t c = (uint32_t)parent.size();
-    parent.push_back(par);
-    tok.push_back(t);
-    ref.push_back(0);
-    nlit.push_back(0);
-    pchild.push_back(0);
-    hf.push_back(NONE);
-    tw.push_back(NONE);
-    tn.push_back(NONE);
-    hcode.push_back(0);
-    sig.push_back(0);
-    slot.push_back(DEAD);
-    fchild.push_back(0);
-    half.push_back(0);
-    keyed.push_back(0);
-    return c;
-  }
-  // home bucket of the edge (par, t): a keyed parent's literal children by token, its '+' child
-  // (probed by IT_PLUS items, never keyed) like every other edge
-  uint64_t home(uint32_t par, uint64_t t) const {
-    return edge_home(par, t, nbk - 1, keyed[par] != 0 && t != PLUS_TOK);
-  }
-  // the root's fat half as the walk's arguments carry it (rh0.z = NONE: none)
-  void root_half(DevIndex& x) const {
-    uint4 sl[2] = {make_uint4(0u, 0u, NONE, 0u), make_uint4(0u, 0u, 0u, 0u)};
-    if (fchild[0]) node_slot(fchild[0], sl);
-    x.rh0 = sl[0];
-    x.rh1 = sl[1];
-  }
-  // the walk's copy of the slot of the only literal child H of the root's half's '+' child
-  // (gm_kernels.h rp0/rp1), derived wherever root_half is, so it follows every change of H's slot
-  // in the same commit; rp0.z = NONE: none.  (H is at depth 3 under a '+' node: never fat, never
-  // a half; checked all the same.)
-  void root_plus_half(DevIndex& x) const {
-    uint4 sl[2] = {make_uint4(0u, 0u, NONE, 0u), make_uint4(0u, 0u, 0u, 0u)};
-    const uint32_t g = fchild[0], p = g ? pchild[g] : 0u;
-    if (p && nlit[p] == 1) {
-      const auto it = lone.find(p);
-      if (it != lone.end() && slot[it->second] != DEAD && parent[it->second] == p &&
-          !half[it->second] && !fchild[it->second])
-        node_slot(it->second, sl);
-    }
-    x.rp0 = sl[0];
-    x.rp1 = sl[1];
-  }
-  bool lone_parent(uint32_t par) const {  // a depth-2 '+' node
-    return par != 0 && tok[par] == PLUS_TOK && parent[par] != 0 && parent[parent[par]] == 0;
-  }
-  void lit_added(uint32_t par, uint32_t c) {  // after nlit[par] += 1 for the new child c
-    if (!lone_parent(par)) return;
-    if (nlit[par] == 1)
-      lone[par] = c;
-    else
-      lone.erase(par);
-  }
-  void lit_removed(uint32_t par) {  // a literal child of par went
-    if (lone_parent(par)) lone.erase(par);
-  }
-  void lone_rebuild() {  // from the node arrays (a snapshot load)
-    lone.clear();
-    for (uint32_t c = 1; c < parent.size(); ++c)
-      if (slot[c] != DEAD && tok[c] != PLUS_TOK && lone_parent(parent[c]) && nlit[parent[c]] == 1)
-        lone[parent[c]] = c;
-  }
-  // a filter was added along path[0] = root .. path[m] (its end node; hash_last: a '#' filter
-  // hanging off path[m]): a code its ancestors can no longer guarantee is reset to unbounded
-  void widen_codes(const std::vector<uint32_t>& path, bool hash_last,
-                   std::vector<uint32_t>& dirty) {
-    const size_t m = path.size() - 1;
-    for (size_t i = 0; i < m; ++i) {
-      const uint32_t x = path[i];
-      if (hcode[x] && (hash_last || m - i > hcode[x])) {
-        hcode[x] = 0;
-        dirty.push_back(x);
-      }
-    }
   }
 };
 
@@ -480,10 +180,6 @@ struct BuildJob {
   std::chrono::steady_clock::time_point t0;
   double build_ms = 0;
 };
-
-inline bool bit(const std::vector<uint64_t>& b, uint64_t i) { return (b[i >> 6] >> (i & 63)) & 1; }
-inline void bset(std::vector<uint64_t>& b, uint64_t i) { b[i >> 6] |= 1ull << (i & 63); }
-inline void bclr(std::vector<uint64_t>& b, uint64_t i) { b[i >> 6] &= ~(1ull << (i & 63)); }
 
 }  // namespace
 
@@ -861,21 +557,6 @@ void free_bufs(std::vector<DevBuf>& v) {
   v.clear();
 }
 
-// Node-level filter list during the build: NONE, a single fid, or LIST_MULTI|index.
-struct ListBuild {
-  std::vector<std::vector<uint32_t>> lists;
-  void add(uint32_t& slot, uint32_t fid) {
-    if (slot == NONE) {
-      slot = fid;
-    } else if (slot & LIST_MULTI) {
-      lists[slot & ~LIST_MULTI].push_back(fid);
-    } else {
-      lists.push_back({slot, fid});
-      slot = LIST_MULTI | (uint32_t)(lists.size() - 1);
-    }
-  }
-};
-
 int patch_wait(emqxgm* h);
 
 // Grow-and-append a device mirror of an append-only host array (bytes [uploaded, total)).
@@ -1010,8 +691,7 @@ void fan_lists(emqxgm* h, uint32_t id, std::vector<uint32_t>& rt, std::vector<ui
       groups.push_back(EMQXGM_DEST_GROUP | d.second);
     }
   }
-  std::sort(groups.begin(), groups.end());
-  groups.erase(std::unique(groups.begin(), groups.end()), groups.end());
+  sort_unique(groups);
   rt.insert(rt.end(), groups.begin(), groups.end());
   if (local) {
     auto sit = h->lsubs.find(id);
@@ -1079,8 +759,7 @@ int fan_commit(emqxgm* h) {
   auto& ch = h->fan_changed;
   if (!m.valid || h->fan_rebuild || (m.cap == 0 && !ch.empty())) return fan_full(h);
   if (ch.empty()) return 0;
-  std::sort(ch.begin(), ch.end());
-  ch.erase(std::unique(ch.begin(), ch.end()), ch.end());
+  sort_unique(ch);
   std::vector<uint32_t> rt, dl, groups, changed;
   uint64_t garbage = m.garbage;
   for (uint32_t id : ch) {
@@ -1193,7 +872,6 @@ int upload_tables(emqxgm* h, const BuildIn& in, TrieModel& m, DevIndex& nx, Owne
     if (m.slot[c] != DEAD && m.slot[c] != ROOTH) m.node_slot(c, &eslots[SLOT_U4 * m.slot[c]]);
   std::vector<uint32_t> tn_of(m.tn_cap, NONE);
   for (size_t i = 0; i < n_nodes; ++i) tn_of[i] = m.tn[i];
-  const uint64_t fmask = in.fmask;
   const uint64_t xcap = m.xcap_p + m.xcap_w;
   std::vector<uint4> xslots(xcap * XBUCKET * XENT_U4, make_uint4(0u, 0u, 0u, 0u));
   for (uint64_t e = 0; e < xcap * XBUCKET; ++e) xslots[XENT_U4 * e].y = bit(m.xtomb, e) ? TOMB : NONE;
@@ -1202,7 +880,7 @@ int upload_tables(emqxgm* h, const BuildIn& in, TrieModel& m, DevIndex& nx, Owne
       if (m.xpos[id] == NONE) continue;
       const Filter& f = F[id - i0];
       const uint8_t* p = pool + f.off;
-      xent(key_hash(p, f.len, fmask), (uint32_t)id, p, f.len, &xslots[XENT_U4 * (uint64_t)m.xpos[id]]);
+      xent(key_hash(p, f.len, in.fmask), (uint32_t)id, p, f.len, &xslots[XENT_U4 * (uint64_t)m.xpos[id]]);
     }
   });
   std::vector<DevBuf> nbufs;
@@ -1225,22 +903,9 @@ int upload_tables(emqxgm* h, const BuildIn& in, TrieModel& m, DevIndex& nx, Owne
   nx.xmask = m.xcap_p - 1;
   nx.xwbase = m.xcap_p;
   nx.xwmask = m.xcap_w - 1;
-  const uint32_t root_p = m.pchild[0];
-  nx.root_cf = m.cf(0);
-  nx.root_sig = m.sig_field(0);
-  nx.root_hf = m.hfd(0);
-  nx.root_pcf = root_p ? m.pcf(root_p) : 0u;
-  nx.root_phf = root_p ? m.phf(root_p) : NONE;
-  m.root_half(nx);
-  m.root_plus_half(nx);
+  m.root_fields(nx);
   nx.test_mask = in.test_mask;
-  nx.needs_verify = m.needs_verify;
-  nx.full_mask = fmask;
-  nx.max_depth = m.max_depth;
-  nx.fid_bound = (uint64_t)m.fv_cap * 32;
-  nx.trie_empty = (m.n_trie == 0);
-  nx.plain_empty = (m.n_route_p == 0);
-  nx.wild_empty = (m.n_route_w == 0);
+  nx.full_mask = in.fmask;
   o = std::make_shared<DevOwner>(std::move(nbufs));
   return 0;
 }
@@ -1269,7 +934,7 @@ BuildIn build_in(emqxgm* h, bool bg) {
   in.nf = h->filters.size();
   in.n_trie_hint = h->n_trie_pending;
   in.test_mask = h->test_mask;
-  in.fmask = h->cfg.full_hash_bits >= 64 ? ~0ull : ((1ull << h->cfg.full_hash_bits) - 1ull);
+  in.fmask = full_mask(h->cfg.full_hash_bits);
   in.fat_mode = h->fat_mode;
   in.keyed_mode = h->keyed_mode;
   return in;
@@ -1287,59 +952,10 @@ int upload_model(emqxgm* h, TrieModel& m) {
   return 0;
 }
 
-// Token-keyed parents (gm_common.h edge_home) of a full build.  mode 1: parents with at least
-// KEYED_MIN_FANOUT literal children, none of whose child tokens is the child of more than
-// KEYED_MAX_SHARE candidates and at most 1/16 of them of more than EBUCKET (their edges then
-// share one bucket per token; the few crowded tokens only lengthen their own chains -- on cfg3 the
-// device ids 0..9999 are also site numbers, children of `site`); mode 2 (tests): every eligible
-// parent; 0: none.  Never the root or a node reached by a '+' edge.
-constexpr uint32_t KEYED_MIN_FANOUT = 16;
-constexpr uint32_t KEYED_MAX_SHARE = 8;
-void select_keyed(TrieModel& m, uint32_t mode) {
-  const size_t nn = m.parent.size();
-  m.keyed.assign(nn, 0u);
-  if (mode == 0) return;
-  auto eligible = [&](uint32_t x) {
-    return x != 0 && m.tok[x] != PLUS_TOK && m.nlit[x] > 0 &&
-           (mode == 2 || m.nlit[x] >= KEYED_MIN_FANOUT);
-  };
-  if (mode == 2) {
-    for (uint32_t x = 1; x < nn; ++x) m.keyed[x] = eligible(x) ? 1 : 0;
-    return;
-  }
-  // child tokens of the candidates, counted by sorting
-  std::vector<uint64_t> toks;
-  for (uint32_t c = 1; c < nn; ++c)
-    if (m.tok[c] != PLUS_TOK && eligible(m.parent[c])) toks.push_back(m.tok[c]);
-  if (toks.empty()) return;
-  std::sort(toks.begin(), toks.end());
-  std::vector<std::pair<uint64_t, uint32_t>> crowded;  // tokens under more than EBUCKET candidates
-  for (size_t i = 0; i < toks.size();) {
-    size_t j = i;
-    while (j < toks.size() && toks[j] == toks[i]) ++j;
-    if (j - i > EBUCKET) crowded.emplace_back(toks[i], (uint32_t)std::min<size_t>(j - i, ~0u));
-    i = j;
-  }
-  std::vector<uint32_t> n_crowded(nn, 0);
-  std::vector<uint8_t> ok(nn, 0);
-  for (uint32_t x = 1; x < nn; ++x) ok[x] = eligible(x) ? 1 : 0;
-  for (uint32_t c = 1; c < nn; ++c) {
-    const uint32_t p = m.parent[c];
-    if (!ok[p] || m.tok[c] == PLUS_TOK) continue;
-    auto it = std::lower_bound(crowded.begin(), crowded.end(), std::make_pair(m.tok[c], 0u));
-    if (it == crowded.end() || it->first != m.tok[c]) continue;
-    if (it->second > KEYED_MAX_SHARE) ok[p] = 0;
-    else n_crowded[p] += 1;
-  }
-  for (uint32_t x = 1; x < nn; ++x) m.keyed[x] = ok[x] && n_crowded[x] * 16 <= m.nlit[x];
-}
-
 // The host model (TrieModel) of a full build of the registry's filters [0, in.nf): trie nodes,
 // edge-slot placement, exact-key placement.  No device work; a background build runs it beside
 // the writers (in.bg, for_slices).
 int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
-  const uint64_t test_mask = in.test_mask;
-  const uint64_t fmask = in.fmask;
   const uint64_t nf = in.nf;
 
   // ---- trie: nodes keyed by (parent, level token); root = node 0 ----
@@ -1347,8 +963,7 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
   m.emap.init(std::max<uint64_t>(1024, in.n_trie_hint * 2));
   ListBuild lb;
   m.fvbits.assign((nf + 31) / 32 + 1, 0u);
-  std::vector<uint64_t> toks;
-  std::vector<uint8_t> is_plus, is_hash;
+  Path path;
   int rc = 0;
   for_slices(h, in.bg, nf, [&](uint64_t i0, uint64_t i1, const Filter* F, const uint8_t* pool) {
     for (uint64_t i = i0; i < i1 && !rc; ++i) {
@@ -1357,18 +972,14 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
       if (in.seen) (*in.seen)[id] = f.in_trie ? 1 : 0;
       if (!f.in_trie) continue;
       ++m.n_trie;
-      bool hashed;
-      tokenize(pool + f.off, f.len, test_mask, toks, is_plus, is_hash, hashed);
-      if (hashed) {
+      resolve(pool + f.off, f.len, in.test_mask, path);
+      if (path.hashed) {
         m.fvbits[id >> 5] |= 1u << (id & 31);
         m.needs_verify = true;
       }
-      const size_t nw = toks.size();
-      const bool hash_last = is_hash[nw - 1];
-      const size_t path_len = hash_last ? nw - 1 : nw;  // '#' last: attach to the parent node
       uint32_t cur = 0;
-      for (size_t w = 0; w < path_len; ++w) {
-        const uint64_t tok = is_plus[w] ? PLUS_TOK : toks[w];
+      for (size_t w = 0; w < path.len; ++w) {
+        const uint64_t tok = path.tok[w];
         bool ins;
         uint32_t* v = m.emap.get_or_insert(cur, tok, ins);
         if (ins) {
@@ -1377,26 +988,16 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
             rc = -E2BIG;
             return;
           }
-          const uint32_t child = m.new_node(cur, tok);
-          *v = child;
-          if (is_plus[w])
-            m.pchild[cur] = child;
-          else {
-            m.nlit[cur] += 1;
-            m.lit_added(cur, child);
-          }
+          *v = m.new_node(cur, tok);
         }
         cur = *v;
         m.ref[cur] += 1;
       }
-      m.max_depth = std::max<uint32_t>(m.max_depth, (uint32_t)path_len);
-      lb.add(hash_last ? m.hf[cur] : f.wild ? m.tw[cur] : m.tn[cur], id);
+      m.max_depth = std::max<uint32_t>(m.max_depth, (uint32_t)path.len);
+      lb.add(m.end_field(cur, path, f.wild), id);
     }
   });
   if (rc) return rc;
-  // child signatures
-  for (size_t y = 1; y < m.parent.size(); ++y)
-    if (m.tok[y] != PLUS_TOK) m.sig[m.parent[y]] |= (uint8_t)sig_bit(m.tok[y]);
   // depth codes: H(x) = how many levels below x the filters under x reach (a '#' filter below
   // x: unbounded), bottom-up over node ids (a parent's id is smaller than its children's)
   {
@@ -1419,14 +1020,14 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
     multi.push_back((uint32_t)lb.lists[i].size());
     multi.insert(multi.end(), lb.lists[i].begin(), lb.lists[i].end());
   }
-  auto resolve = [&](uint32_t& v) {
+  auto flat = [&](uint32_t& v) {
     if (v != NONE && (v & LIST_MULTI)) v = LIST_MULTI | list_pos[v & ~LIST_MULTI];
   };
   const size_t n_nodes = m.parent.size();
   for (size_t i = 0; i < n_nodes; ++i) {
-    resolve(m.hf[i]);
-    resolve(m.tw[i]);
-    resolve(m.tn[i]);
+    flat(m.hf[i]);
+    flat(m.tw[i]);
+    flat(m.tn[i]);
   }
   m.n_edges = n_nodes - 1;
   m.multi = std::move(multi);
@@ -1470,6 +1071,7 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
     }
     bset(m.occ, q);
     bset(m.occ, q + 1);
+    m.n_occ += 2;
     m.slot[c] = q;
     m.slot[m.fchild[c]] = q + 1;
   }
@@ -1477,24 +1079,9 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
   // the children of keyed parents before the other thin edges, so that the edges sharing a token
   // find their home bucket free and share its line
   for (int pass = 0; pass < 2; ++pass)
-    for (uint32_t c = 1; c < n_nodes; ++c) {
-      if (m.fchild[c] || m.half[c] || (m.keyed[m.parent[c]] != 0) != (pass == 0)) continue;
-      uint64_t b = m.home(m.parent[c], m.tok[c]), i;
-      for (;;) {
-        uint32_t j = 0;
-        while (j < EBUCKET && bit(m.occ, b * EBUCKET + j) && !bit(m.tomb, b * EBUCKET + j)) ++j;
-        if (j < EBUCKET) {
-          i = b * EBUCKET + j;
-          break;
-        }
-        b = (b + 1) & (m.nbk - 1);
-      }
-      bset(m.occ, i);
-      bclr(m.tomb, i);
-      m.slot[c] = i;
-    }
-  m.n_occ = 0;
-  for (uint64_t w : m.occ) m.n_occ += (uint64_t)__builtin_popcountll(w);
+    for (uint32_t c = 1; c < n_nodes; ++c)
+      if (!m.fchild[c] && !m.half[c] && (m.keyed[m.parent[c]] != 0) == (pass == 0))
+        m.slot[c] = m.place_edge(m.parent[c], m.tok[c], nullptr);
   if (!m.closed_rebuild()) return fail(h, hipErrorUnknown, "edge placement: a slot off its chain");
   // node side array with headroom for delta-commit growth
   m.tn_cap = n_nodes + std::max<uint64_t>(4096, n_nodes / 4);
@@ -1530,26 +1117,10 @@ int build_model(emqxgm* h, const BuildIn& in, TrieModel& m) {
       for (uint64_t k = k0; k < k1; ++k) {
         const uint32_t id = rids[k];
         const Filter& f = F[id];
-        const uint64_t fh = key_hash(pool + f.off, f.len, fmask);
-        const bool w = f.wild;
-        uint64_t b = m.xhome(w, fh);
-        for (;;) {
-          uint32_t j = 0;
-          while (j < XBUCKET && bit(m.xocc, b * XBUCKET + j)) ++j;
-          if (j < XBUCKET) {
-            const uint64_t e = b * XBUCKET + j;
-            bset(m.xocc, e);
-            m.xpos[id] = (uint32_t)e;
-            break;
-          }
-          bset(m.xovf, b);  // the key goes on past this full bucket
-          b = m.xnext(w, b);
-        }
+        m.xpos[id] = (uint32_t)m.place_key(f.wild, key_hash(pool + f.off, f.len, in.fmask), nullptr);
       }
     });
   }
-  m.x_occ_p = m.n_route_p;
-  m.x_occ_w = m.n_route_w;
   return 0;
 }
 
@@ -1573,19 +1144,6 @@ int commit_full(emqxgm* h) {
   return 0;
 }
 
-// Delta commit: apply the membership changes since the last commit to the host model and patch
-// the device tables in place (k_patch).  Returns 0 when applied, 1 when the delta does not fit
-// (too large, a table would pass its load bound, a node list would need a multi[] list, ...):
-// the caller then runs the full build, which also rebuilds the model.  The patches are only
-// staged here; publish_epoch applies them on the GPU after every pass already enqueued and before
-// every later one, so no match sees a half-applied delta.
-//
-// The model's state per filter is its committed flags -- or, for the catch-up of a background
-// build (install_build), `base`: the membership the build read (bit 0 trie, bit 1 route key;
-// ids past its end: none).  The declines for size and for table capacity come before anything
-// changes, so they leave the model valid (a background build then runs while later deltas still
-// patch it); only a delta that would need a multi[] list (level-token collisions) gives the model
-// up half-way.
 // The verify-bit array of the writer's index regrown to `need` words plus headroom: a new
 // buffer (owner o_fv until the next full build brings its own) filled from the host model; the
 // epochs reading the old array keep it.
@@ -1606,109 +1164,105 @@ int grow_fv(emqxgm* h, TrieModel& m, uint64_t need) {
   return 0;
 }
 
-int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
+// Delta commit: apply the membership changes since the last commit to the host model and patch
+// the device tables in place (k_patch).  Returns 0 when applied, 1 when the delta does not fit
+// (too large, a table would pass its load bound, a node list would need a multi[] list, ...):
+// the caller then runs the full build, which also rebuilds the model.  The patches are only
+// staged here; publish_epoch applies them on the GPU after every pass already enqueued and before
+// every later one, so no match sees a half-applied delta.
+//
+// Three steps over one working set (Delta): delta_plan (the model's trie and tables are only
+// read), delta_apply (the model alone: no handle, no device) and delta_stage.
+struct XE {
+  uint4 e[XENT_U4];
+};
+struct Delta {
+  std::vector<uint32_t> tadd, tdel, radd, rdel;  // filter ids joining / leaving the trie, the keys
+  Path path;                                      // the filter at hand (one object: no allocation
+  std::vector<uint32_t> nodes;                    // per filter), the nodes along it
+  EdgePatch epatch;                               // edge slot -> node (NONE: TOMB)
+  std::unordered_map<uint64_t, XE> xpatch;        // exact entry -> content
+  std::vector<uint32_t> dirty;                    // nodes whose slot / side entry changed
+  std::vector<uint32_t> fv_words;   // changed words of the verify bitmap
+  std::vector<uint32_t> ovf_words;  // changed words of the exact table's overflow bitmap
+  std::vector<uint64_t> opened;     // buckets an insert went past: closed no longer
+};
+
+// Step 1: the changes, and whether they fit (0; 1: declined, nothing changed, the model stays
+// valid and a background build runs while later deltas still patch it).  The model's state per
+// filter is its committed flags -- or, for the catch-up of a background build (install_build),
+// `base`: the membership the build read (bit 0 trie, bit 1 route key; ids past its end: none).
+int delta_plan(emqxgm* h, const std::vector<uint8_t>* base, Delta& d) {
   TrieModel& m = h->tm;
-  if (!m.valid || h->delta_mode == 0) return 1;
-  const uint64_t nf = h->filters.size();
-  auto& ch = h->changed;
-  std::sort(ch.begin(), ch.end());
-  ch.erase(std::unique(ch.begin(), ch.end()), ch.end());
-  std::vector<uint32_t> tadd, tdel, radd, rdel;
-  for (uint32_t id : ch) {
+  const Filter* F = h->filters.data();
+  sort_unique(h->changed);
+  for (uint32_t id : h->changed) {
     const Filter& f = h->filters[id];
     const uint8_t b = base ? (id < base->size() ? (*base)[id] : 0u)
                            : (uint8_t)((f.trie_committed ? 1u : 0u) | (f.route_committed ? 2u : 0u));
-    if ((bool)f.in_trie != (bool)(b & 1)) (f.in_trie ? tadd : tdel).push_back(id);
+    if ((bool)f.in_trie != (bool)(b & 1)) (f.in_trie ? d.tadd : d.tdel).push_back(id);
     const bool r = f.route_refs > 0;
-    if (r != (bool)(b & 2)) (r ? radd : rdel).push_back(id);
+    if (r != (bool)(b & 2)) (r ? d.radd : d.rdel).push_back(id);
   }
-  const uint64_t nchg = tadd.size() + tdel.size() + radd.size() + rdel.size();
+  const uint64_t nchg = d.tadd.size() + d.tdel.size() + d.radd.size() + d.rdel.size();
   if (h->delta_mode == 1 &&
       nchg > (h->delta_max ? h->delta_max : std::max<uint64_t>(4096, (m.n_trie + m.n_route) / 8)))
     return 1;
+  const uint64_t nf = h->filters.size();
   if ((nf + 31) / 32 + 1 > m.fv_cap) {
     // filter ids registered past the verify bits' headroom (a bulk registration, whose build
     // runs in the background): a larger array, from the host model
     if (int rc = grow_fv(h, m, (nf + 31) / 32 + 1)) return rc;
   }
-
-  const uint64_t test_mask = h->test_mask;
-  std::vector<uint64_t> toks;
-  std::vector<uint8_t> is_plus, is_hash;
-  {
-    // the nodes and slots the delta can take at most: each added filter's path levels that are
-    // not in the trie yet, plus every node a delete may free and an add re-create
-    // (and a fat half moved out of its parent's bucket where the first new node is a second
-    // literal child: one more slot)
-    uint64_t new_nodes = 0, moved = 0, xa[2] = {0, 0};
-    std::unordered_map<uint32_t, uint32_t> dpass;  // node -> deleted filters passing it
-    auto walk = [&](uint32_t id, auto&& on_node) {
-      const Filter& f = h->filters[id];
-      bool hashed;
-      tokenize(h->pool.data() + f.off, f.len, test_mask, toks, is_plus, is_hash, hashed);
-      const size_t path_len = is_hash.back() ? toks.size() - 1 : toks.size();
-      uint32_t cur = 0;
-      size_t w = 0;
-      for (; w < path_len; ++w) {
-        const uint32_t* v = m.emap.find(cur, is_plus[w] ? PLUS_TOK : toks[w]);
-        if (!v) break;
-        cur = *v;
-        on_node(cur);
-      }
-      new_nodes += path_len - w;
-      if (w < path_len && !is_plus[w] && m.fchild[cur]) moved += 1;
-    };
-    if (!tadd.empty())
-      for (uint32_t id : tdel) walk(id, [&](uint32_t n) { dpass[n] += 1; });
-    new_nodes = moved = 0;
-    for (uint32_t id : tadd)
-      walk(id, [&](uint32_t n) {  // a node the deletes free is created again
-        auto it = dpass.find(n);
-        if (it != dpass.end() && it->second >= m.ref[n]) new_nodes += 1;
-      });
-    if (m.parent.size() + new_nodes > std::min<uint64_t>(MAX_NODES, m.tn_cap) ||
-        (m.n_occ + new_nodes + moved) * 2 > m.ecap)
-      return 1;
-    for (uint32_t id : radd) xa[h->filters[id].wild ? 1 : 0] += 1;
-    for (int w = 0; w < 2; ++w)
-      if (xa[w] && (m.xoccr(w != 0) + xa[w]) * 4 > m.xcapr(w != 0) * XBUCKET * 3) return 1;
-  }
-  m.valid = false;  // from here a declined delta leaves the model to the full build
-
-  const uint64_t fmask =
-      h->cfg.full_hash_bits >= 64 ? ~0ull : ((1ull << h->cfg.full_hash_bits) - 1ull);
-  std::unordered_map<uint64_t, uint32_t> epatch;  // edge slot -> node (NONE: TOMB)
-  struct XE {
-    uint4 e[XENT_U4];
+  // the nodes and slots the delta can take at most: each added filter's path levels that are
+  // not in the trie yet, plus every node a delete may free and an add re-create (and a fat half
+  // moved out of its parent's bucket where the first new node is a second literal child: a slot)
+  uint64_t new_nodes = 0, moved = 0, xa[2] = {0, 0};
+  std::unordered_map<uint32_t, uint32_t> dpass;  // node -> deleted filters passing it
+  auto walk = [&](uint32_t id, auto&& on_node) {
+    resolve(h->pool.data() + F[id].off, F[id].len, h->test_mask, d.path);
+    m.follow(d.path, d.nodes);
+    for (size_t k = 1; k < d.nodes.size(); ++k) on_node(d.nodes[k]);
+    const size_t w = d.nodes.size() - 1;
+    new_nodes += d.path.len - w;
+    if (w < d.path.len && d.path.tok[w] != PLUS_TOK && m.fchild[d.nodes.back()]) moved += 1;
   };
-  std::unordered_map<uint64_t, XE> xpatch;        // exact entry -> content
-  std::vector<uint32_t> dirty;                    // nodes whose slot / side entry changed
-  std::vector<uint32_t> fv_words;  // changed words of the verify bitmap
-  std::vector<uint32_t> ovf_words; // changed words of the exact table's overflow bitmap
-  std::vector<uint32_t> path;
+  if (!d.tadd.empty())
+    for (uint32_t id : d.tdel) walk(id, [&](uint32_t n) { dpass[n] += 1; });
+  new_nodes = moved = 0;
+  for (uint32_t id : d.tadd)
+    walk(id, [&](uint32_t n) {  // a node the deletes free is created again
+      auto it = dpass.find(n);
+      if (it != dpass.end() && it->second >= m.ref[n]) new_nodes += 1;
+    });
+  if (m.parent.size() + new_nodes > std::min<uint64_t>(MAX_NODES, m.tn_cap) ||
+      (m.n_occ + new_nodes + moved) * 2 > m.ecap)
+    return 1;
+  for (uint32_t id : d.radd) xa[F[id].wild ? 1 : 0] += 1;
+  for (int w = 0; w < 2; ++w)
+    if (xa[w] && (m.xoccr(w != 0) + xa[w]) * 4 > m.xcapr(w != 0) * XBUCKET * 3) return 1;
+  return 0;
+}
 
+// Step 2: the changes applied to the model; the registry as for_slices hands it to build_model
+// (F[id], pool + F[id].off; nf filters).  1: a delta the model cannot take after all (a multi[]
+// list at a filter's end node, a cap met on the way); the caller gives the model up.
+int delta_apply(TrieModel& m, Delta& d, const Filter* F, const uint8_t* pool, uint64_t nf,
+                uint64_t test_mask, uint64_t fmask) {
+  Path& path = d.path;
+  std::vector<uint32_t>& nodes = d.nodes;
   // ---- trie deletes: drop the key from its end node, free nodes no filter passes any more ----
-  for (uint32_t id : tdel) {
-    const Filter& f = h->filters[id];
-    bool hashed;
-    tokenize(h->pool.data() + f.off, f.len, test_mask, toks, is_plus, is_hash, hashed);
-    const size_t nw = toks.size();
-    const bool hash_last = is_hash[nw - 1];
-    const size_t path_len = hash_last ? nw - 1 : nw;
-    path.clear();
-    uint32_t cur = 0;
-    for (size_t w = 0; w < path_len; ++w) {
-      const uint32_t* v = m.emap.find(cur, is_plus[w] ? PLUS_TOK : toks[w]);
-      if (!v) return 1;
-      cur = *v;
-      path.push_back(cur);
-    }
-    uint32_t& fld = hash_last ? m.hf[cur] : f.wild ? m.tw[cur] : m.tn[cur];
+  for (uint32_t id : d.tdel) {
+    resolve(pool + F[id].off, F[id].len, test_mask, path);
+    m.follow(path, nodes);
+    if (nodes.size() <= path.len) return 1;
+    const uint32_t cur = nodes.back();
+    uint32_t& fld = m.end_field(cur, path, F[id].wild);
     if (fld != id) return 1;  // part of a multi[] list
     fld = NONE;
-    dirty.push_back(cur);
-    for (size_t k = path.size(); k-- > 0;) {
-      const uint32_t n = path[k];
+    d.dirty.push_back(cur);
+    for (size_t k = nodes.size(); k-- > 1;) {
+      const uint32_t n = nodes[k];
       if (--m.ref[n] != 0) continue;
       const uint32_t par = m.parent[n];
       m.emap.erase(par, m.tok[n]);
@@ -1722,208 +1276,145 @@ int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
         m.fchild[par] = 0;
         m.half[n] = 0;
       }
-      if (m.slot[n] != ROOTH) {
-        bset(m.tomb, m.slot[n]);
-        epatch[m.slot[n]] = NONE;
-        m.owner[m.slot[n]] = NONE;
-      }
+      m.free_edge(n, d.epatch);
       m.slot[n] = DEAD;
       m.n_edges -= 1;
-      dirty.push_back(par);
+      d.dirty.push_back(par);
     }
     m.n_trie -= 1;
   }
 
-  // ---- trie inserts: new nodes take the first free or TOMB slot of their bucket chain ----
-  // (a bucket the new edge passes is no longer closed, gm_common.h EDGE_CLOSED: the slots that
-  // carried its mark are re-emitted with this commit's patches, below)
-  std::vector<uint64_t> opened;
-  auto alloc_slot = [&](uint32_t par, uint64_t tok) {
-    uint64_t b = m.home(par, tok), i = DEAD;
-    while (i == DEAD) {
-      for (uint32_t j = 0; j < EBUCKET && i == DEAD; ++j) {
-        const uint64_t q = b * EBUCKET + j;
-        if (!bit(m.occ, q)) {
-          bset(m.occ, q);
-          m.n_occ += 1;
-          i = q;
-        } else if (bit(m.tomb, q)) {
-          bclr(m.tomb, q);
-          i = q;
-        }
-      }
-      if (i == DEAD && !bit(m.open, b)) {
-        bset(m.open, b);
-        opened.push_back(b);
-      }
-      b = (b + 1) & (m.nbk - 1);
-    }
-    return i;
+  // ---- trie inserts: new nodes take the first free or TOMB slot of their bucket chain
+  // (TrieModel::place_edge; the slots of the buckets it opens are re-emitted by delta_stage) ----
+  auto seat = [&](uint32_t c) {
+    m.slot[c] = m.place_edge(m.parent[c], m.tok[c], &d.opened);
+    m.owner[m.slot[c]] = c;
+    d.epatch[m.slot[c]] = c;
   };
-  for (uint32_t id : tadd) {
-    const Filter& f = h->filters[id];
-    bool hashed;
-    tokenize(h->pool.data() + f.off, f.len, test_mask, toks, is_plus, is_hash, hashed);
-    if (hashed) {
+  for (uint32_t id : d.tadd) {
+    resolve(pool + F[id].off, F[id].len, test_mask, path);
+    if (path.hashed) {
       m.fvbits[id >> 5] |= 1u << (id & 31);
       m.needs_verify = true;
-      fv_words.push_back(id >> 5);
+      d.fv_words.push_back(id >> 5);
     }
-    const size_t nw = toks.size();
-    const bool hash_last = is_hash[nw - 1];
-    const size_t path_len = hash_last ? nw - 1 : nw;
     uint32_t cur = 0;
-    path.assign(1, 0u);  // root .. end node
-    for (size_t w = 0; w < path_len; ++w) {
-      const uint64_t tok = is_plus[w] ? PLUS_TOK : toks[w];
+    nodes.assign(1, 0u);  // root .. end node
+    for (size_t w = 0; w < path.len; ++w) {
+      const uint64_t tok = path.tok[w];
       bool ins;
       uint32_t* v = m.emap.get_or_insert(cur, tok, ins);
       if (ins) {
         if (m.parent.size() >= std::min<uint64_t>(MAX_NODES, m.tn_cap)) return 1;
         if ((m.n_occ + 1) * 2 > m.ecap) return 1;  // load bound of a delta-patched table
         const uint32_t fc = m.fchild[cur];
-        if (fc && !is_plus[w]) {
+        if (fc && tok != PLUS_TOK) {
           // a second literal child: the fat half moves to its own hash position (its old slot
           // becomes TOMB), so cur's literal children are probed by hash from now on
           if ((m.n_occ + 2) * 2 > m.ecap) return 1;
-          if (m.slot[fc] != ROOTH) {
-            bset(m.tomb, m.slot[fc]);
-            epatch[m.slot[fc]] = NONE;
-            m.owner[m.slot[fc]] = NONE;
-          }
+          m.free_edge(fc, d.epatch);
           m.half[fc] = 0;
           m.fchild[cur] = 0;
-          m.slot[fc] = alloc_slot(cur, m.tok[fc]);
-          m.owner[m.slot[fc]] = fc;
-          epatch[m.slot[fc]] = fc;
-          dirty.push_back(fc);
+          seat(fc);
+          d.dirty.push_back(fc);
         }
-        const uint32_t c = m.new_node(cur, tok);
-        *v = c;
-        const uint64_t i = alloc_slot(cur, tok);
-        m.slot[c] = i;
-        m.owner[i] = c;
-        epatch[i] = c;
+        const uint32_t c = *v = m.new_node(cur, tok);
+        seat(c);
         m.n_edges += 1;
-        if (is_plus[w]) {
-          m.pchild[cur] = c;
-        } else {
-          m.nlit[cur] += 1;
-          m.lit_added(cur, c);
-          m.sig[cur] |= (uint8_t)sig_bit(tok);
-        }
-        dirty.push_back(cur);
-        dirty.push_back(c);
+        d.dirty.push_back(cur);
+        d.dirty.push_back(c);
       }
       cur = *v;
       m.ref[cur] += 1;
-      path.push_back(cur);
+      nodes.push_back(cur);
     }
-    m.max_depth = std::max<uint32_t>(m.max_depth, (uint32_t)path_len);
-    uint32_t& fld = hash_last ? m.hf[cur] : f.wild ? m.tw[cur] : m.tn[cur];
+    m.max_depth = std::max<uint32_t>(m.max_depth, (uint32_t)path.len);
+    uint32_t& fld = m.end_field(cur, path, F[id].wild);
     if (fld != NONE) return 1;  // a second key at one node needs a multi[] list
     fld = id;
-    m.widen_codes(path, hash_last, dirty);
-    dirty.push_back(cur);
+    m.widen_codes(nodes, path.hash_last, d.dirty);
+    d.dirty.push_back(cur);
     m.n_trie += 1;
   }
 
   // ---- exact route keys ----
   m.xpos.resize(nf, NONE);
-  for (uint32_t id : rdel) {
+  for (uint32_t id : d.rdel) {
     const uint32_t e = m.xpos[id];
     if (e == NONE) return 1;
     bset(m.xtomb, e);
-    xpatch[e] = XE{{make_uint4(0u, TOMB, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)}};
+    d.xpatch[e] = XE{{make_uint4(0u, TOMB, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)}};
     m.xpos[id] = NONE;
     m.n_route -= 1;
-    m.nroute(h->filters[id].wild) -= 1;
+    m.nroute(F[id].wild) -= 1;
   }
-  for (uint32_t id : radd) {
-    const Filter& f = h->filters[id];
+  for (uint32_t id : d.radd) {
+    const Filter& f = F[id];
     const bool w = f.wild;
     if ((m.xoccr(w) + 1) * 4 > m.xcapr(w) * XBUCKET * 3) return 1;
-    const uint64_t fh = key_hash(h->pool.data() + f.off, f.len, fmask);
-    uint64_t b = m.xhome(w, fh), e = DEAD;
-    while (e == DEAD) {
-      for (uint32_t j = 0; j < XBUCKET && e == DEAD; ++j) {
-        const uint64_t q = b * XBUCKET + j;
-        if (!bit(m.xocc, q)) {
-          bset(m.xocc, q);
-          m.xoccr(w) += 1;
-          e = q;
-        } else if (bit(m.xtomb, q)) {
-          bclr(m.xtomb, q);
-          e = q;
-        }
-      }
-      if (e == DEAD && !bit(m.xovf, b)) {  // the key goes on past this full bucket
-        bset(m.xovf, b);
-        ovf_words.push_back((uint32_t)(b >> 5));
-      }
-      b = m.xnext(w, b);
-    }
-    xent(fh, id, h->pool.data() + f.off, f.len, xpatch[e].e);
+    const uint64_t fh = key_hash(pool + f.off, f.len, fmask);
+    const uint64_t e = m.place_key(w, fh, &d.ovf_words);
+    xent(fh, id, pool + f.off, f.len, d.xpatch[e].e);
     m.xpos[id] = (uint32_t)e;
     m.n_route += 1;
     m.nroute(w) += 1;
   }
+  return 0;
+}
 
-  // ---- patch lists: a dirty node rewrites its own slot, and its parent's slot when it is the
-  // parent's '+' child (the parent's slot carries its {cf, hf}, and lends its signature when
-  // the parent has no literal child: sig_field -- a '+' node that gains a literal child is
-  // dirty, so the lent bits follow in the same commit) ----
-  std::sort(dirty.begin(), dirty.end());
-  dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
-  std::vector<uint32_t> tn_nodes;
-  for (uint32_t n : dirty) {
+// Step 3: what delta_apply left to be written goes into the handle's patch list (one upload,
+// one launch: publish_epoch) with the pool's and the fan-out tables' own changes.
+int delta_stage(emqxgm* h, Delta& d) {
+  TrieModel& m = h->tm;
+  // a dirty node rewrites its own slot, and its parent's slot when it is the parent's '+' child
+  // (the parent's slot carries its {cf, hf}, and lends its signature when the parent has no
+  // literal child: sig_field -- a '+' node that gains a literal child is dirty, so the lent bits
+  // follow in the same commit)
+  PatchList& pl = h->patches;
+  sort_unique(d.dirty);
+  for (uint32_t n : d.dirty) {
     if (n != 0 && m.slot[n] == DEAD) continue;  // removed
-    if (n != 0 && m.slot[n] != ROOTH) epatch[m.slot[n]] = n;  // ROOTH: the arguments, below
-    tn_nodes.push_back(n);
+    if (n != 0 && m.slot[n] != ROOTH) d.epatch[m.slot[n]] = n;  // ROOTH: the arguments, below
+    pl.add(m.d_tn + n, &m.tn[n], 1);
     const uint32_t par = n ? m.parent[n] : NONE;
     if (par != NONE && par != 0 && m.pchild[par] == n && m.slot[par] != ROOTH)
-      epatch[m.slot[par]] = par;
+      d.epatch[m.slot[par]] = par;
   }
-  for (uint64_t b : opened)
+  // a bucket a new edge went past is no longer closed (gm_common.h EDGE_CLOSED): the slots that
+  // carried its mark are written again
+  for (uint64_t b : d.opened)
     for (uint32_t j = 0; j < EBUCKET; ++j)
-      if (m.owner[b * EBUCKET + j] != NONE) epatch[b * EBUCKET + j] = m.owner[b * EBUCKET + j];
-  // ---- stage the patches, upload them in one copy, apply them in one launch ----
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, hipErrorInvalidDevice, "hipSetDevice");
-  PatchList& pl = h->patches;
-  for (const auto& p : epatch) {
+      if (m.owner[b * EBUCKET + j] != NONE) d.epatch[b * EBUCKET + j] = m.owner[b * EBUCKET + j];
+  for (const auto& p : d.epatch) {
     uint4 sl[2] = {make_uint4(0u, 0u, TOMB, 0u), make_uint4(0u, 0u, 0u, 0u)};
     if (p.second != NONE) m.node_slot(p.second, sl);
     pl.add(m.d_edges + 8 * p.first, sl, 8);
   }
-  for (const auto& p : xpatch) pl.add(m.d_exact + 4 * XENT_U4 * p.first, p.second.e, 4 * XENT_U4);
-  for (uint32_t n : tn_nodes) pl.add(m.d_tn + n, &m.tn[n], 1);
-  std::sort(fv_words.begin(), fv_words.end());
-  fv_words.erase(std::unique(fv_words.begin(), fv_words.end()), fv_words.end());
-  for (uint32_t w : fv_words) pl.add(m.d_fv + w, &m.fvbits[w], 1);
-  std::sort(ovf_words.begin(), ovf_words.end());
-  ovf_words.erase(std::unique(ovf_words.begin(), ovf_words.end()), ovf_words.end());
-  for (uint32_t w : ovf_words) {
+  for (const auto& p : d.xpatch) pl.add(m.d_exact + 4 * XENT_U4 * p.first, p.second.e, 4 * XENT_U4);
+  sort_unique(d.fv_words);
+  for (uint32_t w : d.fv_words) pl.add(m.d_fv + w, &m.fvbits[w], 1);
+  sort_unique(d.ovf_words);
+  for (uint32_t w : d.ovf_words) {
     const uint32_t v = (uint32_t)(m.xovf[w >> 1] >> (32 * (w & 1)));
     pl.add(m.d_xovf + w, &v, 1);
   }
-  int rc = 0;
-  if ((rc = upload_pool(h, &pl)) || (rc = fan_commit(h))) return rc;
+  if (int rc = upload_pool(h, &pl)) return rc;
+  if (int rc = fan_commit(h)) return rc;
+  m.root_fields(h->ix);
+  return 0;
+}
 
-  DevIndex& ix = h->ix;
-  const uint32_t root_p = m.pchild[0];
-  ix.root_cf = m.cf(0);
-  ix.root_sig = m.sig_field(0);
-  ix.root_hf = m.hfd(0);
-  ix.root_pcf = root_p ? m.pcf(root_p) : 0u;
-  ix.root_phf = root_p ? m.phf(root_p) : NONE;
-  m.root_half(ix);
-  m.root_plus_half(ix);
-  ix.needs_verify = m.needs_verify;
-  ix.max_depth = m.max_depth;
-  ix.fid_bound = (uint64_t)m.fv_cap * 32;
-  ix.trie_empty = (m.n_trie == 0);
-  ix.plain_empty = (m.n_route_p == 0);
-  ix.wild_empty = (m.n_route_w == 0);
+int commit_delta(emqxgm* h, const std::vector<uint8_t>* base = nullptr) {
+  TrieModel& m = h->tm;
+  if (!m.valid || h->delta_mode == 0) return 1;
+  Delta d;
+  if (int rc = delta_plan(h, base, d)) return rc;
+  m.valid = false;  // from here a declined delta leaves the model to the full build
+  if (delta_apply(m, d, h->filters.data(), h->pool.data(), h->filters.size(), h->test_mask,
+                  full_mask(h->cfg.full_hash_bits)))
+    return 1;
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, hipErrorInvalidDevice, "hipSetDevice");
+  if (int rc = delta_stage(h, d)) return rc;
   m.valid = true;  // h->changed: their committed flags follow at publish (commit_locked)
   return 0;
 }
@@ -3745,8 +3236,7 @@ int emqxgm_route_dests_batch(emqxgm_t* h, const uint8_t* bytes, const uint64_t* 
     for (uint64_t i = i0; i < (sync ? n : std::min(n, i0 + SET_SLICE)); ++i) {
       ds.clear();
       for (uint32_t j = dptr[i]; j < dptr[i + 1]; ++j) ds.emplace_back(node[j], group[j]);
-      std::sort(ds.begin(), ds.end());
-      ds.erase(std::unique(ds.begin(), ds.end()), ds.end());
+      sort_unique(ds);
       const uint8_t* p = bytes + offsets[i];
       const uint32_t len = (uint32_t)(offsets[i + 1] - offsets[i]);
       if (!ds.empty() && h->filters.size() >= 0x7FFFFFFFu) {
@@ -3792,8 +3282,7 @@ int emqxgm_subscribers_batch(emqxgm_t* h, const uint8_t* bytes, const uint64_t* 
     std::unique_lock<std::shared_mutex> g(h->pmu);
     for (uint64_t i = i0; i < (sync ? n : std::min(n, i0 + SET_SLICE)); ++i) {
       ss.assign(subs + sptr[i], subs + sptr[i + 1]);
-      std::sort(ss.begin(), ss.end());
-      ss.erase(std::unique(ss.begin(), ss.end()), ss.end());
+      sort_unique(ss);
       const uint8_t* p = bytes + offsets[i];
       const uint32_t len = (uint32_t)(offsets[i + 1] - offsets[i]);
       if (!ss.empty() && h->filters.size() >= 0x7FFFFFFFu) {
@@ -4241,7 +3730,7 @@ int emqxgm_match_device(emqxgm_t* h, const uint8_t* d_bytes, const uint32_t* d_o
 int emqxgm_key_owners(emqxgm_t* h, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
                       uint32_t parts, uint32_t* owner) {
   if (!h || !offsets || !owner || parts == 0 || (!bytes && n && offsets[n])) return -EINVAL;
-  const uint64_t fmask = h->cfg.full_hash_bits >= 64 ? ~0ull : ((1ull << h->cfg.full_hash_bits) - 1ull);
+  const uint64_t fmask = full_mask(h->cfg.full_hash_bits);
   for (uint64_t i = 0; i < n; ++i) {
     if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 65535) return -EINVAL;
     const uint64_t fh = key_hash(bytes + offsets[i], (uint32_t)(offsets[i + 1] - offsets[i]), fmask);

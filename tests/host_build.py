@@ -18,8 +18,8 @@ ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
 LINKED = [os.path.join(H, "fake_hip.cpp"), os.path.join(ROOT, "oracle", "ref_trie.cpp")]
 DEPS = LINKED + [os.path.join(ROOT, "include", "emqx_gpumatch.h")] + [
     os.path.join(H, f) for f in ("fakehip/hip/hip_runtime.h", "harness_walk.h", "harness_rig.h")] + [
-    os.path.join(CSRC, f) for f in ("gm_engine.cpp", "gm_common.h", "gm_kernels.h", "gm_internal.h",
-                                    "gm_roctx.h")]
+    os.path.join(CSRC, f) for f in ("gm_engine.cpp", "gm_model.h", "gm_common.h", "gm_kernels.h",
+                                    "gm_internal.h", "gm_roctx.h")]
 
 
 def build(main, san="asan", deps=()):
