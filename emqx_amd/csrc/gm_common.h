@@ -209,20 +209,58 @@ constexpr uint32_t X_WILDPEND = 0xFFFFFFFDu;
 constexpr uint32_t VREC = 64;
 constexpr uint32_t VINL = 60;
 
-// Per-topic record written by the tokenizer, 64 B = REC_U4 x uint4:
-//   {wbase, n_words | flags << 24, tok0.lo, tok0.hi} {tok1, tok2} {tok3, tok4} {tok5, tok6}
+// Per-topic record written by the tokenizer, 64 B = REC_U4 x uint4 parts:
+//   {tok0, tok1} {tok2, tok3} {tok4, tok5} {tok6.lo, tok6.hi, wbase, n_words | flags << 24}
 // (tokens past the last level are 0); level tokens from REC_TOKS on are read from the token
 // array at wbase.  Topics have at most 32,768 levels (65,535 bytes).  Stored in blocks of
 // REC_BLOCK topics, part-major within a block (r06): part c of topic t at uint4 index
 // (t / 64) * 256 + c * 64 + t % 64, so a wave's lanes, holding consecutive topics, read and write
 // whole lines per 16-B access, and one address with immediate offsets of 1 KB reaches every part.
 // A scratch of n topics holds ceil(n / 64) whole blocks.
+// A pass stores and loads only the parts its index can read (rec_parts below): the walk reads
+// level token k only where the index has a literal edge at level k, that is for k < max_depth,
+// and wbase only for levels from REC_TOKS on.  With fewer than REC_U4 parts the header word
+// n_words | flags << 24 travels in a u32 per topic beside the records (Scratch::hdr), the
+// block stride stays REC_U4 parts, and the walk takes the tokens not stored as 0.
 constexpr uint32_t REC_U4 = 4;
 constexpr uint32_t REC_BLOCK = 64;
 constexpr uint32_t REC_TOKS = 7;
+constexpr uint32_t REC_PARTS_MIN = 3;  // the walk has two record readers: 3 parts and all 4
 template <class T>
 GM_HD T* rec_at(T* rec, uint32_t t) {
   return rec + (uint64_t)(t / REC_BLOCK) * (REC_BLOCK * REC_U4) + (t % REC_BLOCK);
+}
+// Parts a pass over an index whose deepest filter has max_depth levels stores and loads:
+// ceil(min(max_depth, REC_TOKS) / 2), at least REC_PARTS_MIN; REC_U4 from 7 levels on (tok6, and
+// wbase for the levels past it, live in the last part).
+GM_HD uint32_t rec_parts(uint32_t max_depth) {
+  const uint32_t p = ((max_depth < REC_TOKS ? max_depth : REC_TOKS) + 1u) / 2u;
+  return p < REC_PARTS_MIN ? REC_PARTS_MIN : p;
+}
+// The walk's load of topic t's record into {a, b, c, d} (U4 = uint4).  FULL: all REC_U4 parts,
+// the header in d.w and wbase in d.z.  Otherwise REC_PARTS_MIN parts and the header word from
+// hdr[t] into d.w: d.x, d.y and d.z keep what the caller put there (0: tok6 and wbase read 0).
+template <bool FULL, class U4>
+GM_HD void rec_load(const U4* rec, const uint32_t* hdr, uint32_t t, U4& a, U4& b, U4& c, U4& d) {
+  const U4* q = rec_at(rec, t);
+  a = q[0];
+  b = q[REC_BLOCK];
+  c = q[2 * REC_BLOCK];
+  if (FULL)
+    d = q[3 * REC_BLOCK];
+  else
+    d.w = hdr[t];
+}
+// Level tokens 0 .. REC_TOKS - 1 of a loaded record.
+template <class U4>
+GM_HD void rec_tokens(const U4& a, const U4& b, const U4& c, const U4& d, uint64_t (&tk)[REC_TOKS]) {
+  tk[0] = ((uint64_t)a.y << 32) | a.x;
+  tk[1] = ((uint64_t)a.w << 32) | a.z;
+  tk[2] = ((uint64_t)b.y << 32) | b.x;
+  tk[3] = ((uint64_t)b.w << 32) | b.z;
+  tk[4] = ((uint64_t)c.y << 32) | c.x;
+  tk[5] = ((uint64_t)c.w << 32) | c.z;
+  tk[6] = ((uint64_t)d.y << 32) | d.x;
 }
 constexpr uint32_t T_WILD = 1u;    // some level is exactly '+' or '#'  -> trie result []
 constexpr uint32_t T_DOLLAR = 2u;  // first byte is '$' -> no root '+'/'#' (emqx_trie.erl:282)

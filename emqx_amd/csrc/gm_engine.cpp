@@ -253,6 +253,7 @@ struct emqxgm {
   uint32_t rp_on = 1;              // the walk uses the root's '+' half (tune "root_plus_half")
   uint32_t ks_on = 1;              // keyed siblings share a loaded line (tune "keyed_share")
   uint32_t cb_on = 1;              // lookups end at closed buckets (tune "closed_buckets")
+  uint32_t rec_parts_tune = 0;     // 0: record parts from the index's depth; 4: full records (tune "rec_parts")
   uint64_t census_depth[2 * CENSUS_DEPTHS] = {};  // the last census pass's loads per level
   uint8_t* d_in_bytes = nullptr;
   uint32_t* d_in_off = nullptr;
@@ -1920,6 +1921,7 @@ int ensure_scratch(emqxgm* h, PassCtx& c, uint32_t n, uint64_t words, uint32_t p
   if ((rc = dev_alloc(h, c, (void**)&s.nw, (size_t)ncap * 4)) ||
       (rc = dev_alloc(h, c, (void**)&s.wh, (size_t)wcap * 8)) ||
       (rc = dev_alloc(h, c, (void**)&s.rec, (size_t)(ncap + REC_BLOCK - 1) / REC_BLOCK * REC_BLOCK * 16 * REC_U4)) ||
+      (rc = dev_alloc(h, c, (void**)&s.hdr, (size_t)(ncap + REC_BLOCK - 1) / REC_BLOCK * REC_BLOCK * 4)) ||
       (rc = dev_alloc(h, c, (void**)&s.cnt, (size_t)ncap * 4)) ||
       (rc = dev_alloc(h, c, (void**)&s.row, (size_t)(ncap + 1) * 4)) ||
       (rc = dev_alloc(h, c, (void**)&s.row2, (size_t)(ncap + 1) * 4)) ||
@@ -2020,6 +2022,9 @@ int pass_enqueue(emqxgm* h, PassCtx& c, const Epoch& E, const uint8_t* d_bytes,
   ix.rp_on = h->rp_on;
   ix.ks_on = h->ks_on;
   ix.cb_on = h->cb_on;
+  // the record parts this pass's k_tok stores and its k_walk loads: both read this copy, so they
+  // agree whatever a commit does to the next epoch's depth (census passes count with the same)
+  ix.rec_parts = h->rec_parts_tune ? h->rec_parts_tune : rec_parts(ix.max_depth);
   // the epoch's uploads / patches must have landed (a full build's have: its wait is skipped)
   if (!E.ready_seen.load(std::memory_order_relaxed)) {
     if (hipEventQuery(E.ready) == hipSuccess)
@@ -3457,6 +3462,17 @@ bool model_consistent(const TrieModel& m, uint64_t n_filters, std::string& why) 
   for (uint32_t v : m.xpos)
     if (v != NONE && v >= xent_n) return bad("key position");
   if (m.max_depth > 65536) return bad("depth");
+  // max_depth decides which record parts a pass moves (gm_common.h rec_parts): an understated
+  // value would lose matches, not fail.  No node lies deeper than the deepest filter ever
+  // committed to this model (a parent's id is below its children's, checked above).
+  {
+    std::vector<uint16_t> depth(n, 0);
+    for (uint64_t c = 1; c < n; ++c) {
+      if (m.parent[c] == NONE) continue;
+      depth[c] = (uint16_t)std::min<uint32_t>(depth[m.parent[c]] + 1u, 0xFFFFu);
+      if (depth[c] > m.max_depth) return bad("depth below a node's");
+    }
+  }
   return true;
 }
 
@@ -4501,6 +4517,12 @@ int emqxgm_tune(emqxgm_t* h, const char* key, int64_t value) {
     if (value < 0 || value > 1) return -EINVAL;
     std::lock_guard<std::mutex> g(h->mmu);
     h->cb_on = (uint32_t)value;
+    return 0;
+  }
+  if (strcmp(key, "rec_parts") == 0) {  // 0 (default): record parts from the index's depth; 4: full records
+    if (value != 0 && value != (int64_t)REC_U4) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->rec_parts_tune = (uint32_t)value;
     return 0;
   }
   if (strcmp(key, "spin_us") == 0) {  // host pipes' waits poll before they block

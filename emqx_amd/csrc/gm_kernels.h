@@ -49,6 +49,9 @@ struct DevIndex {
   uint32_t rp_on = 1;     // 0: the walk ignores rp0/rp1 (tune "root_plus_half", A/B)
   uint32_t ks_on = 1;     // 0: keyed siblings each take a probe (tune "keyed_share", A/B)
   uint32_t cb_on = 1;     // 0: the walk ignores closed-bucket marks (tune "closed_buckets", A/B)
+  // topic-record parts a pass's k_tok stores and its k_walk loads (gm_common.h rec_parts); set
+  // by the engine per pass from max_depth (tune "rec_parts"); REC_U4: full records
+  uint32_t rec_parts = 4;
 };
 
 // Layout of the staged pairs of one pass.  Wide: {topic, filter, rank | REJ_BIT}, 12 B.  Packed
@@ -71,6 +74,7 @@ struct Scratch {
   uint32_t* nw = nullptr;     // [n]   words per topic
   uint64_t* wh = nullptr;     // [w]   level tokens
   uint4* rec = nullptr;       // [n * REC_U4] 64-B topic records (gm_common.h)
+  uint32_t* hdr = nullptr;    // [n]   record header words of passes with fewer than REC_U4 parts
   uint32_t* cnt = nullptr;    // [n]   trie matches per topic
   uint32_t* row = nullptr;    // [n+1]
   uint32_t* row2 = nullptr;   // [n+1] (legacy fix-up)
@@ -175,7 +179,8 @@ WalkGeom walk_geometry(int device, uint32_t wg_per_cu);
 hipError_t launch_scan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tmp,
                        uint32_t* total_dst, hipStream_t s);
 uint32_t scan_tmp_words(uint32_t n);
-// tokenise: levels (nw), 64-B topic records (rec: first REC_TOKS tokens inline), tokens of
+// tokenise: levels (nw), 64-B topic records (rec: first REC_TOKS tokens inline; ix.rec_parts
+// parts of each, and the header words in hdr when those are fewer than REC_U4), tokens of
 // deeper levels (wh, at off[t] + t + level); exact route-key ids (exact_id, NONE if absent)
 // of wildcard names when there are no plain keys, else X_WILDPEND marks for launch_exact.
 // src_bytes / src_off (copy-through, TokArgs): the input is read there (pinned host memory) and

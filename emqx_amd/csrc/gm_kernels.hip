@@ -584,6 +584,7 @@ hipError_t launch_tok(const uint8_t* bytes, const uint32_t* off, uint32_t n, con
   a.test_mask = ix.test_mask;
   a.wild_empty = ix.wild_empty;
   a.nt_rec = n >= TOK_NT_MIN;
+  a.hdr = ix.rec_parts >= REC_U4 ? nullptr : sc.hdr;
   const dim3 grid(grid_for(n, 8192));
   const ExactArgs X = exact_args(ix, sc.xseq);
   if (a.cp_bytes) {
@@ -715,6 +716,7 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
                        uint32_t stat_chunks) {
   WalkArgs a;
   a.rec = sc.rec;
+  a.hdr = sc.hdr;
   a.wh = sc.wh;
   a.edges = ix.edges;
   a.emask = ix.emask;
@@ -758,25 +760,36 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
   a.keyed_share = ix.ks_on;
   a.closed_off = ix.cb_on ? 0u : 1u;
   const dim3 grid(blocks);
+  // the record reader: all REC_U4 parts, or REC_PARTS_MIN and the header array (rec_parts never
+  // gives fewer; the pass's k_tok stored by the same ix.rec_parts)
+  const bool full = ix.rec_parts >= REC_U4;
+#define GM_WALK(CENSUS, SPILL, STK, CPT, PAIR)                                                   \
+  do {                                                                                           \
+    if (full)                                                                                    \
+      hipLaunchKernelGGL((k_walk<CENSUS, SPILL, STK, CPT, PAIR, true>), grid, dim3(WG), 0, s, a);  \
+    else                                                                                         \
+      hipLaunchKernelGGL((k_walk<CENSUS, SPILL, STK, CPT, PAIR, false>), grid, dim3(WG), 0, s, a); \
+  } while (0)
   if (census) {
     if (level >= WALK_SPILL)
-      hipLaunchKernelGGL((k_walk<true, true, SP>), grid, dim3(WG), 0, s, a);
+      GM_WALK(true, true, SP, false, false);
     else if (level == WALK_DEEP)
-      hipLaunchKernelGGL((k_walk<true, false, DP, C>), grid, dim3(WG), 0, s, a);
+      GM_WALK(true, false, DP, C, false);
     else
-      hipLaunchKernelGGL((k_walk<true, false, SH, C>), grid, dim3(WG), 0, s, a);
+      GM_WALK(true, false, SH, C, false);
   } else {
     if (level >= WALK_SPILL)
-      hipLaunchKernelGGL((k_walk<false, true, SP>), grid, dim3(WG), 0, s, a);
+      GM_WALK(false, true, SP, false, false);
     else if (level == WALK_DEEP && pair)
-      hipLaunchKernelGGL((k_walk<false, false, DP, C, true>), grid, dim3(WG), 0, s, a);
+      GM_WALK(false, false, DP, C, true);
     else if (level == WALK_DEEP)
-      hipLaunchKernelGGL((k_walk<false, false, DP, C>), grid, dim3(WG), 0, s, a);
+      GM_WALK(false, false, DP, C, false);
     else if (pair)
-      hipLaunchKernelGGL((k_walk<false, false, SH, C, true>), grid, dim3(WG), 0, s, a);
+      GM_WALK(false, false, SH, C, true);
     else
-      hipLaunchKernelGGL((k_walk<false, false, SH, C>), grid, dim3(WG), 0, s, a);
+      GM_WALK(false, false, SH, C, false);
   }
+#undef GM_WALK
   return hipGetLastError();
 }
 

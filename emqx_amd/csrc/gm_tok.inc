@@ -5,8 +5,9 @@
 //   1. their packed bytes are staged in LDS with coalesced 16-B loads;
 //   2. each lane computes its level tokens (gm_common.h word_token), the wildcard flag
 //      (emqx_topic:wildcard/1, :54-64), the '$' flag (emqx_trie.erl:282) and the whole-topic
-//      hash, and writes its 64-B topic record: header + the first REC_TOKS tokens, which is
-//      all the walk reads for topics of up to 7 levels.  A deeper topic writes its levels
+//      hash, and writes its topic record: header + the first REC_TOKS tokens, which is
+//      all the walk reads for topics of up to 7 levels -- of its 64 B only the parts the
+//      committed index can read (gm_common.h rec_parts).  A deeper topic writes its levels
 //      >= REC_TOKS to the token array at off[t] + t (no counters: a topic has <= len + 1 levels).
 // The kernel issues no atomics: a single hot counter serialises at ~88 updates/us chip-wide.
 //   3. the exact route-key probe: when the committed index has plain (non-wildcard) route keys,
@@ -82,6 +83,8 @@ struct TokArgs {
   uint32_t* ctl_host;  // the host mirror of ctl: its CTL_LEGACY is zeroed here (k_scatter<true>
                        // mirrors every other word; scatter blocks set this one), or null
   bool nt_rec;  // records stored non-temporally (batches of at least TOK_NT_MIN topics)
+  uint32_t* hdr;  // null: all REC_U4 record parts are stored (gm_common.h rec_parts); else
+                  // REC_PARTS_MIN, and the header word n_words | flags << 24 of topic t at hdr[t]
 };
 
 // Batches from which k_tok stores its records non-temporally: 128 MB of records and up do not
@@ -331,23 +334,36 @@ __device__ __forceinline__ uint32_t tok_words_rec(const uint32_t* w, uint32_t s,
 }
 
 
-// Topic t's record (gm_common.h rec_at); non-temporal for large batches (nt_rec: records are
-// read back once, by the walk, and would evict its edges)
-__device__ __forceinline__ void store_rec(const TokArgs& A, uint32_t t, uint4 r0, uint4 r1, uint4 r2,
-                                          uint4 r3) {
+// Topic t's record (gm_common.h rec_at): all REC_U4 parts {tok0, tok1} {tok2, tok3} {tok4, tok5}
+// {tok6, wbase, header}, or (A.hdr set) the first REC_PARTS_MIN and the header word to hdr[t]
+// (lanes of consecutive topics fill whole lines there too).  Non-temporal for large batches
+// (nt_rec: records are read back once, by the walk, and would evict its edges).
+__device__ __forceinline__ void store_rec(const TokArgs& A, uint32_t t, const uint64_t (&tk)[REC_TOKS],
+                                          uint32_t wb, uint32_t hd) {
   uint4* q = rec_at(A.rec, t);
   constexpr uint32_t S = REC_BLOCK;
+  const bool full = A.hdr == nullptr;  // (wave-uniform)
+  const uint4 r0 = make_uint4((uint32_t)tk[0], (uint32_t)(tk[0] >> 32), (uint32_t)tk[1], (uint32_t)(tk[1] >> 32));
+  const uint4 r1 = make_uint4((uint32_t)tk[2], (uint32_t)(tk[2] >> 32), (uint32_t)tk[3], (uint32_t)(tk[3] >> 32));
+  const uint4 r2 = make_uint4((uint32_t)tk[4], (uint32_t)(tk[4] >> 32), (uint32_t)tk[5], (uint32_t)(tk[5] >> 32));
+  const uint4 r3 = make_uint4((uint32_t)tk[6], (uint32_t)(tk[6] >> 32), wb, hd);
   if (A.nt_rec) {
     typedef unsigned int u4v __attribute__((ext_vector_type(4)));
     __builtin_nontemporal_store(u4v{r0.x, r0.y, r0.z, r0.w}, (u4v*)q);
     __builtin_nontemporal_store(u4v{r1.x, r1.y, r1.z, r1.w}, (u4v*)(q + S));
     __builtin_nontemporal_store(u4v{r2.x, r2.y, r2.z, r2.w}, (u4v*)(q + 2 * S));
-    __builtin_nontemporal_store(u4v{r3.x, r3.y, r3.z, r3.w}, (u4v*)(q + 3 * S));
+    if (full)
+      __builtin_nontemporal_store(u4v{r3.x, r3.y, r3.z, r3.w}, (u4v*)(q + 3 * S));
+    else
+      __builtin_nontemporal_store(hd, A.hdr + t);
   } else {
     q[0] = r0;
     q[S] = r1;
     q[2 * S] = r2;
-    q[3 * S] = r3;
+    if (full)
+      q[3 * S] = r3;
+    else
+      A.hdr[t] = hd;
   }
 }
 
@@ -404,11 +420,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_
       __syncthreads();  // every lane is done with the tile's bytes
       if (t < t1) {
         A.nw[t] = nwd;
-        const uint4 r0 = make_uint4(wb, nwd | (flags << 24), (uint32_t)tk[0], (uint32_t)(tk[0] >> 32));
-        const uint4 r1 = make_uint4((uint32_t)tk[1], (uint32_t)(tk[1] >> 32), (uint32_t)tk[2], (uint32_t)(tk[2] >> 32));
-        const uint4 r2 = make_uint4((uint32_t)tk[3], (uint32_t)(tk[3] >> 32), (uint32_t)tk[4], (uint32_t)(tk[4] >> 32));
-        const uint4 r3 = make_uint4((uint32_t)tk[5], (uint32_t)(tk[5] >> 32), (uint32_t)tk[6], (uint32_t)(tk[6] >> 32));
-        store_rec(A, t, r0, r1, r2, r3);
+        store_rec(A, t, tk, wb, nwd | (flags << 24));
         if (flags & T_WILD) {
           if (DEFER)
             hit = X_WILDPEND;
@@ -441,10 +453,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_
       const GlobBytes P{A.bytes + b};
       const uint32_t nwd = tok_words(P, len, A.test_mask, dst, flags);
       A.nw[t] = nwd;
-      store_rec(A, t, make_uint4(wb, nwd | (flags << 24), (uint32_t)tk0, (uint32_t)(tk0 >> 32)),
-                make_uint4((uint32_t)tk1, (uint32_t)(tk1 >> 32), (uint32_t)tk2, (uint32_t)(tk2 >> 32)),
-                make_uint4((uint32_t)tk3, (uint32_t)(tk3 >> 32), (uint32_t)tk4, (uint32_t)(tk4 >> 32)),
-                make_uint4((uint32_t)tk5, (uint32_t)(tk5 >> 32), (uint32_t)tk6, (uint32_t)(tk6 >> 32)));
+      const uint64_t tk[REC_TOKS] = {tk0, tk1, tk2, tk3, tk4, tk5, tk6};
+      store_rec(A, t, tk, wb, nwd | (flags << 24));
       if (flags & T_WILD) {
         if (DEFER)
           hit = X_WILDPEND;

@@ -50,6 +50,7 @@ static_assert(CF_ID_MASK == (1u << CPT_SHIFT) - 1 && (IT_TN >> CPT_SHIFT) == 16u
 
 struct WalkArgs {
   const uint4* rec;     // REC_U4 parts per topic, in blocks of 64 topics part-major (rec_at)
+  const uint32_t* hdr;  // per topic n_words | flags << 24, when the pass stored fewer parts
   const uint64_t* wh;   // level tokens
   const uint4* edges;
   uint64_t emask;
@@ -91,13 +92,13 @@ struct WalkArgs {
 // measured slower (profiles/r05/ab_nt).
 // (One address and the parts at immediate offsets of 1 KB: a separate 64-bit address per part,
 // for a fully part-major layout, cost the walk 6 VGPRs, past 128.)
-__device__ __forceinline__ void load_rec(const uint4* rec, uint32_t t, uint4& a, uint4& b, uint4& c,
+// FULLREC (a k_walk template parameter): the pass stored all REC_U4 parts; otherwise
+// REC_PARTS_MIN parts and the header word in A.hdr (gm_common.h rec_parts, rec_load) -- one line
+// per 64 topics less to request, and the registers of tok6 and wbase are constants.
+template <bool FULLREC>
+__device__ __forceinline__ void load_rec(const WalkArgs& A, uint32_t t, uint4& a, uint4& b, uint4& c,
                                          uint4& d) {
-  const uint4* q = rec_at(rec, t);
-  a = q[0];
-  b = q[REC_BLOCK];
-  c = q[2 * REC_BLOCK];
-  d = q[3 * REC_BLOCK];
+  rec_load<FULLREC>(A.rec, A.hdr, t, a, b, c, d);
 }
 
 struct WaveOut {  // wave-uniform cursor into this wave's reserved chunk of staged pairs
@@ -401,7 +402,7 @@ __device__ __forceinline__ uint32_t pair_xchg(uint32_t v) {
 // Only slot 0 anchors a shared line: its fields are read at a constant index (a select between
 // two P[] fields puts the array into scratch).  A slot that has moved along a chain is not at an
 // item's home and shares nothing.
-template <bool CENSUS, bool SPILL, uint32_t STK, bool CPT = false, bool PAIR = false>
+template <bool CENSUS, bool SPILL, uint32_t STK, bool CPT = false, bool PAIR = false, bool FULLREC = true>
 __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
   static_assert(!(CPT && SPILL), "compact items live in LDS only");
   static_assert(!PAIR || (CPT && !SPILL && !CENSUS), "pairs: the compact LDS-only production walk");
@@ -479,20 +480,17 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
     if (t == NONE && nxt != NONE) {
       t = nxt;
       nxt = NONE;
-      wb = nr0.x;
-      L.n = nr0.y & 0xFFFFFFu;
-      L.fl = nr0.y >> 24;
+      wb = nr3.z;  // (0 without the last part: no item of a level >= REC_TOKS then)
+      L.n = nr3.w & 0xFFFFFFu;
+      L.fl = nr3.w >> 24;
       rank = 0;
       L.sp = 0;
       if (L.fl & T_WILD) {  // emqx_trie.erl:157-166: wildcard topic name -> []
         A.cnt[t] = 0;
         t = NONE;
       } else {
-        const uint64_t tk[REC_TOKS] = {
-            ((uint64_t)nr0.w << 32) | nr0.z, ((uint64_t)nr1.y << 32) | nr1.x,
-            ((uint64_t)nr1.w << 32) | nr1.z, ((uint64_t)nr2.y << 32) | nr2.x,
-            ((uint64_t)nr2.w << 32) | nr2.z, ((uint64_t)nr3.y << 32) | nr3.x,
-            ((uint64_t)nr3.w << 32) | nr3.z};
+        uint64_t tk[REC_TOKS];
+        rec_tokens(nr0, nr1, nr2, nr3, tk);
         L.cls = 0;
 #pragma unroll
         for (uint32_t k = 0; k < REC_TOKS; ++k) {
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
     if (A.static_one && !done) {
       if ((PAIR ? L.gl >> 1 : L.gl) < A.n) {
         nxt = PAIR ? L.gl >> 1 : L.gl;
-        load_rec(A.rec, nxt, nr0, nr1, nr2, nr3);
+        load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);
       }
       done = true;
     }
@@ -557,7 +555,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
       const uint32_t r = mbcnt64(mi);
       if (lead && nxt == NONE && r < avail) {
         nxt = q_next + r;
-        load_rec(A.rec, nxt, nr0, nr1, nr2, nr3);  // consumed when this lane next idles
+        load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);  // consumed when this lane next idles
       }
       q_next += min((uint32_t)__popcll(mi), avail);
       mi = __ballot(lead && nxt == NONE);
@@ -567,7 +565,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         const uint32_t ln = pair_xchg(nxt);
         if (!lead && nxt == NONE && ln != NONE) {
           nxt = ln;
-          load_rec(A.rec, nxt, nr0, nr1, nr2, nr3);
+          load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);
         }
       }
     }

@@ -698,6 +698,10 @@ int emqxgm_set_profiling(emqxgm_t* h, int on);
  * ends there when the bucket's line says that no edge was placed past it; 0: the marks
  * are ignored and every such lookup goes on to the next bucket -- an A/B switch like the two above,
  * from the next pass on, same rows; the pair walk is built without the rule);
+ * "rec_parts" (0 default: a pass's tokenizer stores, and its walk loads, only the 16-B parts of
+ * each 64-B topic record that the committed index can read -- three of four, and a 4-B header
+ * word, while no trie filter has 7 levels or more; 4: full records always -- an A/B
+ * switch from the next pass on, same rows, same order, every walk variant and the census);
  * "host_out" (host pipes copy results to the
  * host with hipMemcpyAsync, 0 default, or with a kernel writing host memory, 1);
  * "walk_pair" (1 default: a batch of at most half the walk grid's lanes is walked by two lanes
