@@ -72,7 +72,7 @@ typedef struct {
   int publish;
 } gm_call;
 
-static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT;
+static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT;
 static ERL_NIF_TERM A_OK, A_ERROR, A_TRUE, A_FALSE, A_MOD, A_ROUTES, A_NONE, A_NODE, A_GROUP, A_SUB,
     A_SPIN_US, A_BG_BUILD, A_PUBLISH, A_UNDEFINED, A_REPORT_THREADS, A_EQ, A_WORDS, A_BINARY,
     A_FAIL_THRESHOLD, A_EAGER;
@@ -1201,13 +1201,157 @@ static ERL_NIF_TERM nif_match_rules(ErlNifEnv* env, int argc, const ERL_NIF_TERM
   return rc ? err_term(env, rc) : res;
 }
 
+/* ---- rule sets: every matching rule per name --------------------------------------------------
+ * emqx_rule_engine:get_rules_for_topic/1 (emqx_rule_engine.erl:198-204), emqx_bridge:
+ * get_matched_egress_bridges/1 (emqx_bridge.erl:342-382) and the exhook / trace filters keep
+ * their rule tables; the `from` filters of the rules are mirrored into an emqxgm_ruleset_t (the
+ * whole list replaced when a rule changes) and ruleset_match/2 returns per name the indices of
+ * the rules it matches, ascending, each once. */
+typedef struct {
+  emqxgm_ruleset_t* r; /* NULL once closed */
+  ErlNifMutex* mu;     /* a match's result lives in the handle's buffers until its next call */
+} gm_ruleset;
+
+static void gm_ruleset_dtor(ErlNifEnv* env, void* obj) {
+  gm_ruleset* g = (gm_ruleset*)obj;
+  (void)env;
+  if (g->r) emqxgm_ruleset_destroy(g->r);
+  if (g->mu) enif_mutex_destroy(g->mu);
+}
+
+static int get_ruleset(ErlNifEnv* env, ERL_NIF_TERM t, gm_ruleset** g) {
+  return enif_get_resource(env, t, RULESET_RT, (void**)g) && (*g)->mu;
+}
+
+/* ruleset_open(Device, WordHashBits) -> {ok, R} | {error, Reason} (WordHashBits: 0 but in tests) */
+static ERL_NIF_TERM nif_ruleset_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  int dev;
+  unsigned bits;
+  (void)argc;
+  if (!enif_get_int(env, argv[0], &dev) || !enif_get_uint(env, argv[1], &bits)) return enif_make_badarg(env);
+  gm_ruleset* g = enif_alloc_resource(RULESET_RT, sizeof(gm_ruleset));
+  memset(g, 0, sizeof *g);
+  g->mu = enif_mutex_create("emqx_trie_gpu.ruleset");
+  const int rc = g->mu ? emqxgm_ruleset_create(dev, bits, &g->r) : -ENOMEM;
+  if (rc) {
+    enif_release_resource(g);
+    return rc == -EINVAL ? enif_make_badarg(env) : err_term(env, rc);
+  }
+  ERL_NIF_TERM t = enif_make_resource(env, g);
+  enif_release_resource(g);
+  return enif_make_tuple2(env, A_OK, t);
+}
+
+/* ruleset_set(R, [Rule :: [{Filter, eq | words | binary}]]) -> ok | {error, Reason}: replaces the
+ * whole list; rule I (from 0) is the I-th element, a rule may be [].  badarg on a malformed list
+ * (the list in force stays). */
+static ERL_NIF_TERM nif_ruleset_set(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_ruleset* g;
+  unsigned nr, nf = 0;
+  (void)argc;
+  if (!get_ruleset(env, argv[0], &g) || !enif_get_list_length(env, argv[1], &nr)) return enif_make_badarg(env);
+  /* the filters of all rules as one list, in order (consed up in reverse, then turned round) */
+  ERL_NIF_TERM rev = enif_make_list(env, 0), flat = enif_make_list(env, 0), l = argv[1], rule, f;
+  for (unsigned i = 0; i < nr; ++i) {
+    unsigned k;
+    enif_get_list_cell(env, l, &rule, &l);
+    if (!enif_get_list_length(env, rule, &k)) return enif_make_badarg(env);
+    nf += k;
+    while (enif_get_list_cell(env, rule, &f, &rule)) rev = enif_make_list_cell(env, f, rev);
+  }
+  while (enif_get_list_cell(env, rev, &f, &rev)) flat = enif_make_list_cell(env, f, flat);
+  packed p;
+  int rc = pack_list(env, flat, 1, &p);
+  uint32_t *o = NULL, *fg = NULL, *fr = NULL;
+  if (!rc) {
+    o = off32(&p);
+    fg = enif_alloc(sizeof(uint32_t) * (nf ? nf : 1));
+    fr = enif_alloc(sizeof(uint32_t) * (nf ? nf : 1));
+    if (!o || !fg || !fr) rc = -ENOMEM;
+  }
+  if (!rc && (p.n != nf || p.off[p.n] > 0xFFFFFFFFull)) rc = -E2BIG;
+  unsigned at = 0;
+  l = argv[1];
+  for (unsigned i = 0; !rc && i < nr; ++i) {
+    enif_get_list_cell(env, l, &rule, &l);
+    while (!rc && enif_get_list_cell(env, rule, &f, &rule)) {
+      int ar;
+      const ERL_NIF_TERM* el;
+      enif_get_tuple(env, f, &ar, &el);
+      if (ar != 2) rc = -EINVAL;
+      else if (el[1] == A_EQ) fg[at] = EMQXGM_RULE_EQ;
+      else if (el[1] == A_WORDS) fg[at] = EMQXGM_RULE_WORDS;
+      else if (el[1] == A_BINARY) fg[at] = 0;
+      else rc = -EINVAL;
+      fr[at++] = i;
+    }
+  }
+  if (!rc) {
+    enif_mutex_lock(g->mu);
+    rc = g->r ? emqxgm_ruleset_set(g->r, p.bytes, o, fg, fr, nf, nr) : -EINVAL;
+    enif_mutex_unlock(g->mu);
+  }
+  enif_free(o);
+  enif_free(fg);
+  enif_free(fr);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* ruleset_match(R, [Name]) -> [[RuleIndex]] | {error, Reason} */
+static ERL_NIF_TERM nif_ruleset_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_ruleset* g;
+  packed p;
+  (void)argc;
+  if (!get_ruleset(env, argv[0], &g)) return enif_make_badarg(env);
+  int rc = pack_list(env, argv[1], 0, &p);
+  uint32_t* o = rc ? NULL : off32(&p);
+  if (!rc && !o) rc = -ENOMEM;
+  if (!rc && p.off[p.n] > 0xFFFFFFFFull) rc = -E2BIG;
+  emqxgm_ruleset_out out;
+  memset(&out, 0, sizeof out);
+  ERL_NIF_TERM res = 0;
+  if (!rc) {
+    enif_mutex_lock(g->mu);
+    rc = g->r ? emqxgm_ruleset_match(g->r, p.bytes, o, p.n, &out) : -EINVAL;
+    if (!rc) {
+      res = enif_make_list(env, 0);
+      for (uint32_t i = out.n; i-- > 0;) {
+        ERL_NIF_TERM row = enif_make_list(env, 0);
+        for (uint64_t j = out.ptr[i + 1]; j-- > out.ptr[i];)
+          row = enif_make_list_cell(env, enif_make_uint(env, out.rule[j]), row);
+        res = enif_make_list_cell(env, row, res);
+      }
+    }
+    enif_mutex_unlock(g->mu);
+  }
+  enif_free(o);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* ruleset_close(R) -> ok: frees the device list now (the resource's destructor otherwise) */
+static ERL_NIF_TERM nif_ruleset_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_ruleset* g;
+  (void)argc;
+  if (!get_ruleset(env, argv[0], &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  if (g->r) emqxgm_ruleset_destroy(g->r);
+  g->r = NULL;
+  enif_mutex_unlock(g->mu);
+  return A_OK;
+}
+
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
   RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu", gm_res_dtor, ERL_NIF_RT_CREATE, NULL);
   CALL_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_call", gm_call_dtor, ERL_NIF_RT_CREATE, NULL);
   RETAIN_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_retain", gm_retain_dtor, ERL_NIF_RT_CREATE, NULL);
-  if (!RT || !CALL_RT || !RETAIN_RT || emqxgm_abi_version() != EMQXGM_ABI_VERSION) return -1;
+  RULESET_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_ruleset", gm_ruleset_dtor, ERL_NIF_RT_CREATE, NULL);
+  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || emqxgm_abi_version() != EMQXGM_ABI_VERSION) return -1;
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
   A_TRUE = enif_make_atom(env, "true");
@@ -1264,6 +1408,10 @@ static ErlNifFunc funcs[] = {
     {"retain_commit", 1, nif_retain_commit, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"retain_match", 3, nif_retain_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_rules", 3, nif_match_rules, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"ruleset_open", 2, nif_ruleset_open, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"ruleset_set", 2, nif_ruleset_set, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"ruleset_match", 2, nif_ruleset_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"ruleset_close", 1, nif_ruleset_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(emqx_trie_gpu_nif, funcs, load, NULL, NULL, NULL)

@@ -11,8 +11,10 @@ from .engine import NONE, AsyncMatcher, AsyncResult, Batcher, DeviceResult, Engi
 from .router import Router, SessionRouter  # noqa: F401
 from .retainer import Retainer  # noqa: F401
 from .rules import TopicRules  # noqa: F401
+from .ruleset import RuleSet, get_matched_egress_bridges, get_rules_for_topic  # noqa: F401
 from .trie import Trie  # noqa: F401
 
 __all__ = ["Engine", "EngineError", "MatchResult", "DeviceResult", "PublishResult", "Trie",
-           "Router", "SessionRouter", "Broker", "TopicRules", "Retainer", "Batcher", "Window",
+           "Router", "SessionRouter", "Broker", "TopicRules", "RuleSet",
+           "get_rules_for_topic", "get_matched_egress_bridges", "Retainer", "Batcher", "Window",
            "AsyncMatcher", "AsyncResult", "NONE"]

@@ -231,6 +231,29 @@ hipError_t launch_retain_runs(const RetainDev& base, const RetainDev& delta, con
                               uint32_t* out, unsigned long long* total, bool fill, hipStream_t s);
 hipError_t launch_retain_ptr(const uint32_t* rbase, const uint32_t* abase, uint32_t n,
                              uint32_t* ptr, hipStream_t s);
+// Rule sets: every matching rule per name (gm_ruleset.inc / gm_ruleset.cpp), device pointers.
+// One pass of names against the resident list: a count launch (cnt), launch_ruleset_ptr (row =
+// exclusive scan of cnt, row[n] = total), a fill launch (rule[row[t] ..)).
+struct RulesetArgs {
+  const uint8_t* nb = nullptr;    // the pass's names
+  const uint32_t* no = nullptr;   // [n+1]
+  uint32_t n = 0;
+  const uint64_t* recs = nullptr; // tiled record stream (gm_ruleset_match.h)
+  uint32_t total_words = 0;
+  const uint8_t* fb = nullptr;    // filter bytes
+  const uint32_t* fo = nullptr;   // [n_filters+1]
+  const uint32_t* ff = nullptr;   // [n_filters] RS_F_* flags
+  uint32_t n_filters = 0;
+  uint64_t test_mask = 0;
+  uint32_t* cnt = nullptr;        // count pass: [n] rules per name
+  const uint32_t* row = nullptr;  // fill pass: [n+1]
+  uint32_t* rule = nullptr;       // fill pass: [row[n]]
+  uint32_t* err = nullptr;        // set when a fill lane and its row disagree (or a bad record)
+  unsigned long long* ctr = nullptr;  // count pass, optional: [4] RS_CTR_*
+};
+hipError_t launch_ruleset(const RulesetArgs& a, bool fill, hipStream_t s);
+hipError_t launch_ruleset_ptr(const uint32_t* cnt, uint32_t* row, uint32_t n, uint32_t* tmp,
+                              uint32_t* total_dst, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

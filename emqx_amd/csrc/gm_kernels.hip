@@ -14,6 +14,7 @@
 #include "gm_common.h"
 #include "gm_kernels.h"
 #include "gm_match.h"
+#include "gm_ruleset_match.h"
 
 namespace gm {
 
@@ -197,6 +198,7 @@ __device__ __forceinline__ uint3 stg_load(const uint3* stg, const StgFmt& F, uin
 #include "gm_fanout.inc"
 #include "gm_rules.inc"
 #include "gm_retain.inc"
+#include "gm_ruleset.inc"
 
 __global__ __launch_bounds__(WG) void k_row64(const uint32_t* row, uint64_t base, uint64_t* out,
                                               uint32_t m) {
@@ -1158,6 +1160,21 @@ hipError_t launch_retain_ptr(const uint32_t* rbase, const uint32_t* abase, uint3
                              uint32_t* ptr, hipStream_t s) {
   hipLaunchKernelGGL(k_retain_ptr, dim3(n / WG + 1), dim3(WG), 0, s, rbase, abase, n, ptr);
   return hipGetLastError();
+}
+
+hipError_t launch_ruleset(const RulesetArgs& a, bool fill, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
+  if (fill)
+    hipLaunchKernelGGL(k_ruleset<true>, grid, dim3(WG), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_ruleset<false>, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ruleset_ptr(const uint32_t* cnt, uint32_t* row, uint32_t n, uint32_t* tmp,
+                              uint32_t* total_dst, hipStream_t s) {
+  return launch_scan(cnt, row, n, tmp, total_dst, s);
 }
 
 }  // namespace gm

@@ -2,8 +2,9 @@
 // level tokens, for rule lists that return every matching rule per name (the
 // rule engine's get_rules_for_topic/1, egress bridges, exhook and trace filters).  Plain
 // functions with no HIP call, written so that a device kernel and a host program run the same
-// code; today the CPU check (tests/host_harness/ruleset_main.cpp, tests/test_ruleset_cpu.py) is
-// their only caller -- no kernel or C-ABI entry uses them yet.
+// code: k_ruleset (gm_ruleset.inc) and the host side of the emqxgm_ruleset_* C-ABI
+// (gm_ruleset.cpp) on the device path, tests/host_harness/ruleset_main.cpp and
+// ruleset_dev_main.cpp (the kernel's phases, lane by lane) on the CPU.
 //
 // A filter of a rule is compiled once into a record of 64-bit words:
 //   word 0   header: levels (5 bits) | RS_* flags (6) | rule index (16) | filter index (20) |
@@ -45,6 +46,14 @@ GM_HD uint64_t rs_header(uint32_t levels, uint32_t flags, uint32_t rule, uint32_
                          uint32_t plus) {
   return (uint64_t)levels | ((uint64_t)flags << 5) | ((uint64_t)rule << 11) |
          ((uint64_t)filter << 27) | ((uint64_t)plus << 47);
+}
+// Tiles of a record stream of total_words words, and the words of tile k that the stream holds
+// (a short last tile: the rest of the LDS tile is set to RS_END).
+GM_HD uint32_t rs_n_tiles(uint32_t total_words) { return (total_words + RS_TILE_WORDS - 1) / RS_TILE_WORDS; }
+GM_HD uint32_t rs_tile_span(uint32_t k, uint32_t total_words) {
+  const uint64_t b = (uint64_t)k * RS_TILE_WORDS;
+  if (b >= total_words) return 0;
+  return total_words - b < RS_TILE_WORDS ? (uint32_t)(total_words - b) : RS_TILE_WORDS;
 }
 GM_HD uint64_t rs_test_mask(uint32_t hash_bits) { return hash_bits ? (1ull << hash_bits) - 1 : 0; }
 

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 5  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 6  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -110,6 +110,11 @@ ASYNC_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(_AsyncWindow))
 class _RetOut(C.Structure):
     _fields_ = [("n", C.c_uint32), ("n_ids", C.c_uint64), ("ptr", C.POINTER(C.c_uint64)),
                 ("id", C.POINTER(C.c_uint32))]
+
+
+class _RulesetOut(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("n_ids", C.c_uint64), ("ptr", C.POINTER(C.c_uint64)),
+                ("rule", C.POINTER(C.c_uint32))]
 
 
 class _Stats(C.Structure):
@@ -205,6 +210,12 @@ SYMBOLS = {
     "emqxgm_retain_read": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),
     "emqxgm_retain_topic": (C.c_int, [_P, C.c_uint32, C.POINTER(_U8P), _U32P]),
     "emqxgm_retain_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, C.POINTER(_RetOut)]),
+    "emqxgm_ruleset_create": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    "emqxgm_ruleset_destroy": (None, [_P]),
+    "emqxgm_ruleset_set": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32]),
+    "emqxgm_ruleset_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_RulesetOut)]),
+    "emqxgm_ruleset_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emqxgm_ruleset_stats": (C.c_int, [_P, _U64P]),
     "emqxgm_batcher_create": (C.c_int, [_P, C.POINTER(_BatcherCfg), C.POINTER(_P)]),
     "emqxgm_batcher_destroy": (None, [_P]),
     "emqxgm_batcher_add": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),

@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 5
+#define EMQXGM_ABI_VERSION 6
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -445,6 +445,47 @@ typedef struct emqxgm_retain_out { /* host-resident, valid until the next call o
 /* match_messages/3 for a batch of filters (packed bytes + [n+1] offsets on the host) */
 int emqxgm_retain_match(emqxgm_retain_t* r, const uint8_t* bytes, const uint32_t* offsets,
                         uint32_t n, uint64_t now_ms, emqxgm_retain_out* out);
+
+/* ---- rule sets: every matching rule per name, against a resident list ----
+ * The loops that keep every match, run once per publish beside the route match:
+ * emqx_rule_engine:get_rules_for_topic/1 (apps/emqx_rule_engine/src/emqx_rule_engine.erl:198-204;
+ * a rule matches when any of its `from` filters does, emqx_plugin_libs_rule.erl:340-346),
+ * emqx_bridge:get_matched_egress_bridges/1 (emqx_bridge.erl:342-382), and the exhook and trace
+ * topic filters (emqx_exhook_server.erl:361, emqx_trace_handler.erl:138: one filter per rule).
+ * The list is compiled once at emqxgm_ruleset_set and stays on the device; a match tokenises
+ * each name once and confirms on the bytes whatever rests on a hashed word.  word_hash_bits is
+ * the test knob of emqxgm_cfg.word_hash_bits (0 = production).  Limits: 65,536 rules and 2^20
+ * filters per list. */
+typedef struct emqxgm_ruleset emqxgm_ruleset_t;
+int emqxgm_ruleset_create(int32_t device, uint32_t word_hash_bits, emqxgm_ruleset_t** out);
+void emqxgm_ruleset_destroy(emqxgm_ruleset_t* r);
+/* Replaces the whole list.  Filter i = filter_bytes[filter_offsets[i] .. filter_offsets[i+1])
+ * with flags 0 (match/2 on binaries) | EMQXGM_RULE_WORDS | EMQXGM_RULE_EQ, belonging to rule
+ * filter_rule[i]; the filters of one rule are adjacent: filter_rule is non-decreasing and
+ * < n_rules.  A rule may have no filter.  -EINVAL beyond the limits or on malformed offsets,
+ * flags or rule order; the previous list then stays in force. */
+int emqxgm_ruleset_set(emqxgm_ruleset_t* r, const uint8_t* filter_bytes,
+                       const uint32_t* filter_offsets, const uint32_t* filter_flags,
+                       const uint32_t* filter_rule, uint32_t n_filters, uint32_t n_rules);
+typedef struct emqxgm_ruleset_out { /* host-resident, valid until the next call on r */
+  uint32_t n;
+  uint64_t n_ids;
+  const uint64_t* ptr;  /* [n+1] */
+  const uint32_t* rule; /* name i matches rule[ptr[i] .. ptr[i+1]), ascending, each once */
+} emqxgm_ruleset_out;
+/* names: packed bytes + [n+1] offsets on the host.  -EIO if the device reports a row that the
+ * count and the fill pass disagree on. */
+int emqxgm_ruleset_match(emqxgm_ruleset_t* r, const uint8_t* bytes, const uint32_t* offsets,
+                         uint32_t n, emqxgm_ruleset_out* out);
+/* "pass_names": names per device pass (default 1 Mi; never more than (2^32 - 1) / n_rules, so a
+ * pass's 32-bit row pointers cannot overflow); "counters": 1 = the count pass keeps the four
+ * counters of emqxgm_ruleset_stats; "timing": 1 = HIP events around the count and the fill
+ * kernel of every pass (tools/ruleset_bench.py), setting it clears the sums, which the read-only
+ * keys "count_us" / "fill_us" return in microseconds (>= 0, the value is ignored) */
+int emqxgm_ruleset_tune(emqxgm_ruleset_t* r, const char* key, int64_t value);
+/* out = {records, record tiles, filters, rules, candidates sent to the byte check, candidates it
+ * removed, names deeper than 16 levels, records visited}; the last four since the last set */
+int emqxgm_ruleset_stats(emqxgm_ruleset_t* r, uint64_t out[8]);
 
 /* ---- single-driver batcher core: publish windows over the host pipes ---------------------
  * A caller that batches topics itself (one thread adding, flushing and collecting; bench.py's

@@ -35,7 +35,11 @@
     retain_clean/1,
     retain_commit/1,
     retain_match/3,
-    match_rules/3
+    match_rules/3,
+    ruleset_open/2,
+    ruleset_set/2,
+    ruleset_match/2,
+    ruleset_close/1
 ]).
 
 -on_load(init/0).
@@ -95,6 +99,16 @@ retain_match(_R, _Filters, _NowMs) -> ?NOT_LOADED.
 %% match_rules(Res, [Name], [{Filter, eq | words | binary}]) -> [Index | none]: the first rule
 %% each name matches (emqx_authz_rule:match_topics/3, emqx_rewrite:match_and_rewrite/3)
 match_rules(_Res, _Names, _Rules) -> ?NOT_LOADED.
+%% ---- rule sets: every matching rule per name (emqx_rule_engine:get_rules_for_topic/1,
+%% emqx_bridge:get_matched_egress_bridges/1, the exhook and trace topic filters) ----
+%% ruleset_open(Device, WordHashBits :: 0) -> {ok, R} | {error, Reason}
+ruleset_open(_Device, _WordHashBits) -> ?NOT_LOADED.
+%% ruleset_set(R, [Rule :: [{Filter, eq | words | binary}]]) -> ok: replaces the whole list
+ruleset_set(_R, _Rules) -> ?NOT_LOADED.
+%% ruleset_match(R, [Name]) -> [[RuleIndex]]: per name the rules it matches, ascending, each once
+ruleset_match(_R, _Names) -> ?NOT_LOADED.
+%% ruleset_close(R) -> ok
+ruleset_close(_R) -> ?NOT_LOADED.
 %% snapshot_save(Res, Path :: binary()) -> ok | {error, Reason}: the committed index to a file
 snapshot_save(_Res, _Path) -> ?NOT_LOADED.
 %% snapshot_load(Res, Path :: binary()) -> ok | {error, Reason}: into a fresh resource, no build
