@@ -72,10 +72,10 @@ typedef struct {
   int publish;
 } gm_call;
 
-static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT;
+static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT, *ACL_RT;
 static ERL_NIF_TERM A_OK, A_ERROR, A_TRUE, A_FALSE, A_MOD, A_ROUTES, A_NONE, A_NODE, A_GROUP, A_SUB,
     A_SPIN_US, A_BG_BUILD, A_PUBLISH, A_UNDEFINED, A_REPORT_THREADS, A_EQ, A_WORDS, A_BINARY,
-    A_FAIL_THRESHOLD, A_EAGER;
+    A_FAIL_THRESHOLD, A_EAGER, A_ALLOW, A_DENY, A_SUBSCRIBE, A_ALL, A_USERNAME, A_CLIENTID, A_SLOT;
 
 static int tab_init(term_tab* t, char* name) {
   t->lk = enif_rwlock_create(name);
@@ -1344,6 +1344,291 @@ static ERL_NIF_TERM nif_ruleset_close(ErlNifEnv* env, int argc, const ERL_NIF_TE
   return A_OK;
 }
 
+/* ---- ACL lists: the first matching authz rule per request ---------------------------------------
+ * emqx_authz_rule:matches/4 (emqx_authz_rule.erl:125-133) for emqx_authz_file:authorize/4
+ * (emqx_authz_file.erl:64-65) and emqx_authz_mnesia:authorize/4 (emqx_authz_mnesia.erl:98-120): the
+ * compiled rules are mirrored into an emqxgm_acl_t (the whole list replaced when a source changes)
+ * and acl_match/2 returns per request the index of the rule that decides it, or none.  The caller
+ * keeps the permissions and evaluates the principals the device does not decide (regexes, ipaddr,
+ * ipaddrs, 'and', 'or': re:run/2 and esockd_cidr:match/2, once per client) into the who bits. */
+typedef struct {
+  emqxgm_acl_t* a; /* NULL once closed */
+  ErlNifMutex* mu;
+} gm_acl;
+
+static void gm_acl_dtor(ErlNifEnv* env, void* obj) {
+  gm_acl* g = (gm_acl*)obj;
+  (void)env;
+  if (g->a) emqxgm_acl_destroy(g->a);
+  if (g->mu) enif_mutex_destroy(g->mu);
+}
+
+static int get_acl(ErlNifEnv* env, ERL_NIF_TERM t, gm_acl** g) {
+  return enif_get_resource(env, t, ACL_RT, (void**)g) && (*g)->mu;
+}
+
+/* acl_open(Device, WordHashBits) -> {ok, A} | {error, Reason} (WordHashBits: 0 but in tests) */
+static ERL_NIF_TERM nif_acl_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  int dev;
+  unsigned bits;
+  (void)argc;
+  if (!enif_get_int(env, argv[0], &dev) || !enif_get_uint(env, argv[1], &bits)) return enif_make_badarg(env);
+  gm_acl* g = enif_alloc_resource(ACL_RT, sizeof(gm_acl));
+  memset(g, 0, sizeof *g);
+  g->mu = enif_mutex_create("emqx_trie_gpu.acl");
+  const int rc = g->mu ? emqxgm_acl_create(dev, bits, &g->a) : -ENOMEM;
+  if (rc) {
+    enif_release_resource(g);
+    return rc == -EINVAL ? enif_make_badarg(env) : err_term(env, rc);
+  }
+  ERL_NIF_TERM t = enif_make_resource(env, g);
+  enif_release_resource(g);
+  return enif_make_tuple2(env, A_OK, t);
+}
+
+/* Element `idx` of every tuple of a list, a binary or the atom undefined (packed as empty, with
+ * `bit` set in flags[i]): bytes / 32-bit offsets allocated with enif_alloc. */
+typedef struct {
+  uint8_t* bytes;
+  uint32_t* off;
+} packed_opt;
+
+static void packed_opt_free(packed_opt* p) {
+  enif_free(p->bytes);
+  enif_free(p->off);
+  memset(p, 0, sizeof *p);
+}
+
+static int pack_opt(ErlNifEnv* env, ERL_NIF_TERM list, unsigned n, int idx, uint32_t* flags, uint32_t bit,
+                    packed_opt* p) {
+  memset(p, 0, sizeof *p);
+  p->off = enif_alloc(sizeof(uint32_t) * ((size_t)n + 1));
+  if (!p->off) return -ENOMEM;
+  p->off[0] = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    ERL_NIF_TERM head, l = list;
+    uint64_t total = 0;
+    for (unsigned i = 0; i < n; ++i) {
+      ErlNifBinary b;
+      int ar;
+      const ERL_NIF_TERM* el;
+      if (!enif_get_list_cell(env, l, &head, &l) || !enif_get_tuple(env, head, &ar, &el) || ar <= idx) return -EINVAL;
+      if (el[idx] == A_UNDEFINED) {
+        flags[i] |= bit;
+        b.size = 0;
+        b.data = NULL;
+      } else if (!enif_inspect_binary(env, el[idx], &b)) {
+        return -EINVAL;
+      }
+      if (pass && b.size) memcpy(p->bytes + total, b.data, b.size);
+      total += b.size;
+      if (total > 0xFFFFFFFFull) return -E2BIG;
+      p->off[i + 1] = (uint32_t)total;
+    }
+    if (!pass) {
+      p->bytes = enif_alloc(total ? total : 1);
+      if (!p->bytes) return -ENOMEM;
+    }
+  }
+  return 0;
+}
+
+/* acl_set(A, [{allow | deny, Who, publish | subscribe | all, [{Filter, eq | words}]}]) -> ok |
+ * {error, Reason}: replaces the whole list; rule I (from 0) is the I-th element.  Who = all |
+ * {username, Bin} | {clientid, Bin} ({eq, _} principals) | {slot, 0..63} (a principal the caller
+ * evaluates).  A filter is the compiled filter joined with "/"; placeholders are found by the
+ * library.  badarg on a malformed list (the list in force stays). */
+static ERL_NIF_TERM nif_acl_set(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acl* g;
+  unsigned nr, nf = 0;
+  (void)argc;
+  if (!get_acl(env, argv[0], &g) || !enif_get_list_length(env, argv[1], &nr)) return enif_make_badarg(env);
+  const size_t rn = nr ? nr : 1;
+  uint32_t* ru = enif_alloc(sizeof(uint32_t) * rn * 4); /* perm, action, who, slot */
+  uint32_t* wo = enif_alloc(sizeof(uint32_t) * (rn + 1));
+  uint8_t* wb = NULL;
+  size_t wcap = 0;
+  int rc = ru && wo ? 0 : -ENOMEM;
+  ERL_NIF_TERM rev = enif_make_list(env, 0), flat = enif_make_list(env, 0), l = argv[1], rule, f;
+  if (!rc) wo[0] = 0;
+  for (unsigned i = 0; !rc && i < nr; ++i) {
+    int ar, war;
+    const ERL_NIF_TERM *el, *wel;
+    unsigned k, slot = 0;
+    ErlNifBinary b;
+    b.size = 0;
+    b.data = NULL;
+    enif_get_list_cell(env, l, &rule, &l);
+    if (!enif_get_tuple(env, rule, &ar, &el) || ar != 4 || !enif_get_list_length(env, el[3], &k)) {
+      rc = -EINVAL;
+      break;
+    }
+    uint32_t *perm = ru + i, *action = ru + rn + i, *who = ru + 2 * rn + i;
+    ru[3 * rn + i] = 0;
+    *perm = el[0] == A_ALLOW ? EMQXGM_ACL_ALLOW : EMQXGM_ACL_DENY;
+    if (el[0] != A_ALLOW && el[0] != A_DENY) rc = -EINVAL;
+    if (el[2] == A_PUBLISH) *action = EMQXGM_ACL_PUBLISH;
+    else if (el[2] == A_SUBSCRIBE) *action = EMQXGM_ACL_SUBSCRIBE;
+    else if (el[2] == A_ALL) *action = EMQXGM_ACL_ALL;
+    else rc = -EINVAL;
+    if (el[1] == A_ALL) *who = EMQXGM_ACL_WHO_ALL;
+    else if (!enif_get_tuple(env, el[1], &war, &wel) || war != 2) rc = -EINVAL;
+    else if (wel[0] == A_SLOT && enif_get_uint(env, wel[1], &slot)) *who = EMQXGM_ACL_WHO_HOST;
+    else if (wel[0] == A_USERNAME && enif_inspect_binary(env, wel[1], &b)) *who = EMQXGM_ACL_WHO_USERNAME;
+    else if (wel[0] == A_CLIENTID && enif_inspect_binary(env, wel[1], &b)) *who = EMQXGM_ACL_WHO_CLIENTID;
+    else rc = -EINVAL;
+    if (rc) break;
+    ru[3 * rn + i] = slot;
+    if ((uint64_t)wo[i] + b.size > 0xFFFFFFFFull) rc = -E2BIG;
+    if (!rc && b.size) {
+      if (wo[i] + b.size > wcap) {
+        wcap = 2 * (wo[i] + b.size);
+        uint8_t* nw = enif_realloc(wb, wcap);
+        if (!nw) rc = -ENOMEM;
+        else wb = nw;
+      }
+      if (!rc) memcpy(wb + wo[i], b.data, b.size);
+    }
+    if (rc) break;
+    wo[i + 1] = wo[i] + (uint32_t)b.size;
+    nf += k;
+    rule = el[3];
+    while (enif_get_list_cell(env, rule, &f, &rule)) rev = enif_make_list_cell(env, f, rev);
+  }
+  while (enif_get_list_cell(env, rev, &f, &rev)) flat = enif_make_list_cell(env, f, flat);
+  packed p;
+  memset(&p, 0, sizeof p);
+  if (!rc) rc = pack_list(env, flat, 1, &p);
+  uint32_t *o = NULL, *fg = NULL, *fr = NULL;
+  if (!rc) {
+    o = off32(&p);
+    fg = enif_alloc(sizeof(uint32_t) * (nf ? nf : 1));
+    fr = enif_alloc(sizeof(uint32_t) * (nf ? nf : 1));
+    if (!o || !fg || !fr) rc = -ENOMEM;
+  }
+  if (!rc && (p.n != nf || p.off[p.n] > 0xFFFFFFFFull)) rc = -E2BIG;
+  unsigned at = 0;
+  l = argv[1];
+  for (unsigned i = 0; !rc && i < nr; ++i) {
+    int ar;
+    const ERL_NIF_TERM* el;
+    enif_get_list_cell(env, l, &rule, &l);
+    enif_get_tuple(env, rule, &ar, &el);
+    rule = el[3];
+    while (!rc && enif_get_list_cell(env, rule, &f, &rule)) {
+      enif_get_tuple(env, f, &ar, &el);
+      if (ar != 2) rc = -EINVAL;
+      else if (el[1] == A_EQ) fg[at] = EMQXGM_RULE_EQ;
+      else if (el[1] == A_WORDS) fg[at] = 0;
+      else rc = -EINVAL;
+      fr[at++] = i;
+    }
+  }
+  if (!rc) {
+    enif_mutex_lock(g->mu);
+    rc = g->a ? emqxgm_acl_set(g->a, p.bytes, o, fg, fr, nf, ru, ru + rn, ru + 2 * rn, ru + 3 * rn, wb, wo, nr)
+              : -EINVAL;
+    enif_mutex_unlock(g->mu);
+  }
+  enif_free(o);
+  enif_free(fg);
+  enif_free(fr);
+  enif_free(ru);
+  enif_free(wo);
+  enif_free(wb);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* acl_match(A, {[{ClientId | undefined, Username | undefined, WhoBits}],
+ *               [{Name, ClientIndex, publish | subscribe}]}) -> [RuleIndex | none] | {error, Reason}:
+ * matches/4 per request; ClientIndex (from 0) points into the call's client list, WhoBits has bit K
+ * set when the client satisfies the list's host slot K. */
+static ERL_NIF_TERM nif_acl_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acl* g;
+  int ar;
+  const ERL_NIF_TERM* arg;
+  unsigned nc;
+  (void)argc;
+  if (!get_acl(env, argv[0], &g) || !enif_get_tuple(env, argv[1], &ar, &arg) || ar != 2 ||
+      !enif_get_list_length(env, arg[0], &nc))
+    return enif_make_badarg(env);
+  packed p;
+  packed_opt ci, us;
+  memset(&ci, 0, sizeof ci);
+  memset(&us, 0, sizeof us);
+  int rc = pack_list(env, arg[1], 1, &p);
+  const size_t cn = nc ? nc : 1, rn = p.n ? p.n : 1;
+  uint32_t* o = rc ? NULL : off32(&p);
+  uint32_t* cf = enif_alloc(sizeof(uint32_t) * cn);
+  uint64_t* wbits = enif_alloc(sizeof(uint64_t) * cn);
+  uint32_t* rq = rc ? NULL : enif_alloc(sizeof(uint32_t) * rn * 3); /* client, action, out */
+  if (!rc && (!o || !cf || !wbits || !rq)) rc = -ENOMEM;
+  if (!rc && p.off[p.n] > 0xFFFFFFFFull) rc = -E2BIG;
+  if (!rc) {
+    memset(cf, 0, sizeof(uint32_t) * cn);
+    rc = pack_opt(env, arg[0], nc, 0, cf, EMQXGM_ACL_NO_CLIENTID, &ci);
+  }
+  if (!rc) rc = pack_opt(env, arg[0], nc, 1, cf, EMQXGM_ACL_NO_USERNAME, &us);
+  ERL_NIF_TERM head, l = arg[0];
+  for (unsigned i = 0; !rc && i < nc; ++i) {
+    const ERL_NIF_TERM* el;
+    ErlNifUInt64 v;
+    enif_get_list_cell(env, l, &head, &l);
+    enif_get_tuple(env, head, &ar, &el);
+    if (ar != 3 || !enif_get_uint64(env, el[2], &v)) rc = -EINVAL;
+    else wbits[i] = v;
+  }
+  l = arg[1];
+  for (unsigned i = 0; !rc && i < p.n; ++i) {
+    const ERL_NIF_TERM* el;
+    unsigned c;
+    enif_get_list_cell(env, l, &head, &l);
+    enif_get_tuple(env, head, &ar, &el);
+    if (ar != 3 || !enif_get_uint(env, el[1], &c)) rc = -EINVAL;
+    else if (el[2] == A_PUBLISH) rq[rn + i] = EMQXGM_ACL_PUBLISH;
+    else if (el[2] == A_SUBSCRIBE) rq[rn + i] = EMQXGM_ACL_SUBSCRIBE;
+    else rc = -EINVAL;
+    if (!rc) rq[i] = c;
+  }
+  ERL_NIF_TERM res = 0;
+  if (!rc) {
+    uint32_t* out = rq + 2 * rn;
+    enif_mutex_lock(g->mu);
+    rc = g->a ? emqxgm_acl_match(g->a, p.bytes, o, p.n, rq, rq + rn, ci.bytes, ci.off, us.bytes, us.off, cf, wbits,
+                                 nc, out)
+              : -EINVAL;
+    enif_mutex_unlock(g->mu);
+    if (!rc) {
+      res = enif_make_list(env, 0);
+      for (uint32_t i = p.n; i-- > 0;)
+        res = enif_make_list_cell(env, out[i] == EMQXGM_NONE ? A_NONE : enif_make_uint(env, out[i]), res);
+    }
+  }
+  enif_free(o);
+  enif_free(cf);
+  enif_free(wbits);
+  enif_free(rq);
+  packed_opt_free(&ci);
+  packed_opt_free(&us);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* acl_close(A) -> ok: frees the device list now (the resource's destructor otherwise) */
+static ERL_NIF_TERM nif_acl_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acl* g;
+  (void)argc;
+  if (!get_acl(env, argv[0], &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  if (g->a) emqxgm_acl_destroy(g->a);
+  g->a = NULL;
+  enif_mutex_unlock(g->mu);
+  return A_OK;
+}
+
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
@@ -1351,7 +1636,9 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   CALL_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_call", gm_call_dtor, ERL_NIF_RT_CREATE, NULL);
   RETAIN_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_retain", gm_retain_dtor, ERL_NIF_RT_CREATE, NULL);
   RULESET_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_ruleset", gm_ruleset_dtor, ERL_NIF_RT_CREATE, NULL);
-  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || emqxgm_abi_version() != EMQXGM_ABI_VERSION) return -1;
+  ACL_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_acl", gm_acl_dtor, ERL_NIF_RT_CREATE, NULL);
+  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || !ACL_RT || emqxgm_abi_version() != EMQXGM_ABI_VERSION)
+    return -1;
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
   A_TRUE = enif_make_atom(env, "true");
@@ -1372,6 +1659,13 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   A_BINARY = enif_make_atom(env, "binary");
   A_PUBLISH = enif_make_atom(env, "publish");
   A_UNDEFINED = enif_make_atom(env, "undefined");
+  A_ALLOW = enif_make_atom(env, "allow");
+  A_DENY = enif_make_atom(env, "deny");
+  A_SUBSCRIBE = enif_make_atom(env, "subscribe");
+  A_ALL = enif_make_atom(env, "all");
+  A_USERNAME = enif_make_atom(env, "username");
+  A_CLIENTID = enif_make_atom(env, "clientid");
+  A_SLOT = enif_make_atom(env, "slot");
   return 0;
 }
 
@@ -1412,6 +1706,10 @@ static ErlNifFunc funcs[] = {
     {"ruleset_set", 2, nif_ruleset_set, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"ruleset_match", 2, nif_ruleset_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"ruleset_close", 1, nif_ruleset_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acl_open", 2, nif_acl_open, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acl_set", 2, nif_acl_set, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acl_match", 2, nif_acl_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acl_close", 1, nif_acl_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(emqx_trie_gpu_nif, funcs, load, NULL, NULL, NULL)

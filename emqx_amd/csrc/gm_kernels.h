@@ -254,6 +254,36 @@ struct RulesetArgs {
 hipError_t launch_ruleset(const RulesetArgs& a, bool fill, hipStream_t s);
 hipError_t launch_ruleset_ptr(const uint32_t* cnt, uint32_t* row, uint32_t n, uint32_t* tmp,
                               uint32_t* total_dst, hipStream_t s);
+// ACL lists: the first matching rule per request (gm_acl.inc / gm_acl.cpp), device pointers.  One
+// launch per pass of requests against the resident list and the call's client table.
+struct AclArgs {
+  const uint8_t* nb = nullptr;      // the pass's names
+  const uint32_t* no = nullptr;     // [n+1]
+  const uint32_t* client = nullptr; // [n] index into the client table
+  const uint32_t* action = nullptr; // [n] ACL_PUBLISH or ACL_SUBSCRIBE
+  uint32_t n = 0;
+  const uint8_t* cb = nullptr;      // client-id bytes
+  const uint32_t* co = nullptr;     // [n_clients+1]
+  const uint8_t* ub = nullptr;      // username bytes
+  const uint32_t* uo = nullptr;     // [n_clients+1]
+  const uint32_t* cf = nullptr;     // [n_clients] ACL_C_*_UNDEF
+  const uint64_t* wbits = nullptr;  // [n_clients] bit k: the client satisfies host slot k
+  uint32_t n_clients = 0;
+  const uint64_t* recs = nullptr;   // tiled record stream (gm_acl_match.h)
+  uint32_t total_words = 0;
+  const uint8_t* fb = nullptr;      // filter bytes
+  const uint32_t* fo = nullptr;     // [n_filters+1]
+  const uint32_t* ff = nullptr;     // [n_filters] RS_F_EQ or RS_F_WORDS
+  uint32_t n_filters = 0;
+  const uint8_t* wb = nullptr;      // who strings
+  const uint32_t* wo = nullptr;     // [n_rules+1]
+  uint32_t n_rules = 0;
+  uint64_t test_mask = 0;
+  uint32_t* out = nullptr;          // [n] first matching rule, NONE if none
+  uint32_t* err = nullptr;          // set on a bad record, client index or action
+  unsigned long long* ctr = nullptr;  // optional: [4] ACL_CTR_*
+};
+hipError_t launch_acl(const AclArgs& a, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

@@ -15,6 +15,7 @@
 #include "gm_kernels.h"
 #include "gm_match.h"
 #include "gm_ruleset_match.h"
+#include "gm_acl_match.h"
 
 namespace gm {
 
@@ -199,6 +200,7 @@ __device__ __forceinline__ uint3 stg_load(const uint3* stg, const StgFmt& F, uin
 #include "gm_rules.inc"
 #include "gm_retain.inc"
 #include "gm_ruleset.inc"
+#include "gm_acl.inc"
 
 __global__ __launch_bounds__(WG) void k_row64(const uint32_t* row, uint64_t base, uint64_t* out,
                                               uint32_t m) {
@@ -1175,6 +1177,13 @@ hipError_t launch_ruleset(const RulesetArgs& a, bool fill, hipStream_t s) {
 hipError_t launch_ruleset_ptr(const uint32_t* cnt, uint32_t* row, uint32_t n, uint32_t* tmp,
                               uint32_t* total_dst, hipStream_t s) {
   return launch_scan(cnt, row, n, tmp, total_dst, s);
+}
+
+hipError_t launch_acl(const AclArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
+  hipLaunchKernelGGL(k_acl, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
 }
 
 }  // namespace gm

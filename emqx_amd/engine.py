@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 6  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 7  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -216,6 +216,13 @@ SYMBOLS = {
     "emqxgm_ruleset_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_RulesetOut)]),
     "emqxgm_ruleset_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "emqxgm_ruleset_stats": (C.c_int, [_P, _U64P]),
+    "emqxgm_acl_create": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    "emqxgm_acl_destroy": (None, [_P]),
+    "emqxgm_acl_set": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint32]),
+    "emqxgm_acl_match": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32,
+                                   _P]),
+    "emqxgm_acl_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emqxgm_acl_stats": (C.c_int, [_P, _U64P]),
     "emqxgm_batcher_create": (C.c_int, [_P, C.POINTER(_BatcherCfg), C.POINTER(_P)]),
     "emqxgm_batcher_destroy": (None, [_P]),
     "emqxgm_batcher_add": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),
@@ -1034,3 +1041,94 @@ class HandleRegistry:
             self.close()
         except Exception:
             pass
+
+
+# include/emqx_gpumatch.h EMQXGM_ACL_*
+ACL_DENY, ACL_ALLOW = 0, 1
+ACL_PUBLISH, ACL_SUBSCRIBE, ACL_ALL = 1, 2, 3
+ACL_WHO_ALL, ACL_WHO_USERNAME, ACL_WHO_CLIENTID, ACL_WHO_HOST = 0, 1, 2, 3
+ACL_NO_CLIENTID, ACL_NO_USERNAME = 1, 2
+ACL_HOST_SLOTS = 64
+ACL_STAT_KEYS = ("records", "tiles", "filters", "rules", "candidates", "removed", "deep", "visited")
+
+
+class Acl:
+    """A compiled ACL rule list resident on the device (emqxgm_acl_*): the first
+    matching rule per request, ``emqx_authz_rule:matches/4``.  This is the C-ABI as it is, on
+    numbers and bytes; ``emqx_amd.authz.AclList`` is the mirror of the Erlang terms on top."""
+
+    def __init__(self, device: int = 0, word_hash_bits: int = 0):
+        self._lib = lib()
+        self._h = None
+        h = C.c_void_p()
+        rc = self._lib.emqxgm_acl_create(device, word_hash_bits, C.byref(h))
+        if rc != 0:
+            raise EngineError(f"emqxgm_acl_create failed: {rc}")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.emqxgm_acl_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int, what: str):
+        if rc < 0:
+            raise EngineError(f"{what} failed: {rc}")
+        return rc
+
+    def set(self, filters: Sequence[bytes], flags: Sequence[int], filter_rule: Sequence[int],
+            perm: Sequence[int], action: Sequence[int], who: Sequence[int], slot: Sequence[int],
+            who_strings: Sequence[bytes]) -> None:
+        """emqxgm_acl_set: filter i (flag RULE_EQ or 0) belongs to rule filter_rule[i]; rule r has
+        perm[r], action[r], who[r], slot[r] and who_strings[r].  A refused list raises and leaves
+        the one in force unchanged."""
+        n_rules = len(perm)
+        assert len(action) == len(who) == len(slot) == len(who_strings) == n_rules
+        fbuf, foff = pack(list(filters), np.uint32)
+        wbuf, woff = pack(list(who_strings), np.uint32)
+        a = [np.asarray(x, np.uint32) for x in (flags, filter_rule, perm, action, who, slot)]
+        self._check(self._lib.emqxgm_acl_set(
+            self._h, _ptr(fbuf), foff.ctypes.data_as(C.c_void_p), _ptr(a[0]), _ptr(a[1]), len(filters),
+            _ptr(a[2]), _ptr(a[3]), _ptr(a[4]), _ptr(a[5]), _ptr(wbuf), woff.ctypes.data_as(C.c_void_p),
+            n_rules), "acl_set")
+
+    def match(self, names: Sequence[bytes], client: Sequence[int], action: Sequence[int],
+              clientids: Sequence[Optional[bytes]], usernames: Sequence[Optional[bytes]],
+              who_bits: Sequence[int]) -> np.ndarray:
+        """emqxgm_acl_match: request i = (names[i], client[i], action[i]); the client table is
+        clientids / usernames (None: undefined) and who_bits.  -> u32 [n], NONE for nomatch."""
+        names = list(names)
+        n, nc = len(names), len(clientids)
+        assert len(usernames) == len(who_bits) == nc and len(client) == len(action) == n
+        buf, off = pack(names, np.uint32)
+        cbuf, coff = pack([c or b"" for c in clientids], np.uint32)
+        ubuf, uoff = pack([u or b"" for u in usernames], np.uint32)
+        cf = np.asarray([(ACL_NO_CLIENTID if c is None else 0) | (ACL_NO_USERNAME if u is None else 0)
+                         for c, u in zip(clientids, usernames)], np.uint32)
+        wb = np.asarray(who_bits, np.uint64)
+        cl = np.asarray(client, np.uint32)
+        ac = np.asarray(action, np.uint32)
+        out = np.full(n, NONE, np.uint32)
+        self._check(self._lib.emqxgm_acl_match(
+            self._h, _ptr(buf), off.ctypes.data_as(C.c_void_p), n, _ptr(cl), _ptr(ac), _ptr(cbuf),
+            coff.ctypes.data_as(C.c_void_p), _ptr(ubuf), uoff.ctypes.data_as(C.c_void_p), _ptr(cf), _ptr(wb),
+            nc, _ptr(out)), "acl_match")
+        return out
+
+    def tune(self, key: str, value: int) -> None:
+        self._check(self._lib.emqxgm_acl_tune(self._h, key.encode(), int(value)), "acl_tune")
+
+    def kernel_time_us(self) -> int:
+        """Kernel microseconds summed since tune("timing", 1)."""
+        return self._check(self._lib.emqxgm_acl_tune(self._h, b"kernel_us", 0), "acl_tune")
+
+    def stats(self) -> dict:
+        a = (C.c_uint64 * 8)()
+        self._check(self._lib.emqxgm_acl_stats(self._h, a), "acl_stats")
+        return dict(zip(ACL_STAT_KEYS, (int(x) for x in a)))

@@ -11,7 +11,8 @@
   matches under ``match/2`` on binaries ('$' clauses apply), or None.
 
 Both are ``TopicRules.first_match`` with the matching flags; the regex rewrite itself and the
-``${clientid}``/``${username}`` placeholder feed (``feed_var/2``) stay with the caller.
+``${clientid}``/``${username}`` placeholder feed (``feed_var/2``) stay with the caller; whole ACL
+lists with clients, actions and principals are ``emqx_amd.authz``.
 """
 from __future__ import annotations
 

@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 6
+#define EMQXGM_ABI_VERSION 7
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -486,6 +486,70 @@ int emqxgm_ruleset_tune(emqxgm_ruleset_t* r, const char* key, int64_t value);
 /* out = {records, record tiles, filters, rules, candidates sent to the byte check, candidates it
  * removed, names deeper than 16 levels, records visited}; the last four since the last set */
 int emqxgm_ruleset_stats(emqxgm_ruleset_t* r, uint64_t out[8]);
+
+/* ---- ACL lists: the first matching authz rule per request, against a resident list ----
+ * emqx_authz_rule:matches/4 (apps/emqx_authz/src/emqx_authz_rule.erl:125-133): an ordered list of
+ * {Permission, Who, Action, TopicFilters}; the first rule whose action (match_action/2, :147-150),
+ * principal (match_who/2, :152-200) and any topic filter (match_topics/3, :202-210) match decides.
+ * It is emqx_authz_file:authorize/4 (emqx_authz_file.erl:64-65) and, with one rule per record
+ * entry, emqx_authz_mnesia:authorize/4 (emqx_authz_mnesia.erl:98-120, 222-229).  Filters are
+ * {eq, F} (word-list equality, compile_topic/1 :98-101) or match by emqx_topic:match/2 on word
+ * lists (:212-215; EMQXGM_RULE_WORDS semantics); a filter with a word that is exactly
+ * ${clientid} or ${username} is a pattern (pattern/1, :109-110) and gets the request's client fed
+ * in on the device (feed_var/2, :217-230): the value is one binary word, so an empty value, "+",
+ * "#" or a value with a '/' equals no name word, and an undefined value leaves the placeholder a
+ * literal word.  The device decides the principals all, {username, {eq, U}} and
+ * {clientid, {eq, C}} (byte equality; an undefined value never matches); every other principal
+ * (regexes, ipaddr, ipaddrs, 'and', 'or') is one of 64 host slots that the caller evaluates once
+ * per client.  No answer rests on a hash.  Limits: 65,536 rules and 2^20 filters per list. */
+#define EMQXGM_ACL_DENY 0u
+#define EMQXGM_ACL_ALLOW 1u
+#define EMQXGM_ACL_PUBLISH 1u   /* action of a rule or a request */
+#define EMQXGM_ACL_SUBSCRIBE 2u
+#define EMQXGM_ACL_ALL 3u       /* action of a rule only */
+#define EMQXGM_ACL_WHO_ALL 0u
+#define EMQXGM_ACL_WHO_USERNAME 1u /* {username, {eq, who string}} */
+#define EMQXGM_ACL_WHO_CLIENTID 2u /* {clientid, {eq, who string}} */
+#define EMQXGM_ACL_WHO_HOST 3u     /* host slot rule_slot[r] < 64 */
+#define EMQXGM_ACL_NO_CLIENTID 1u  /* client flag: clientid => undefined */
+#define EMQXGM_ACL_NO_USERNAME 2u  /* client flag: username => undefined */
+typedef struct emqxgm_acl emqxgm_acl_t;
+int emqxgm_acl_create(int32_t device, uint32_t word_hash_bits, emqxgm_acl_t** out);
+void emqxgm_acl_destroy(emqxgm_acl_t* a);
+/* Replaces the whole list (compile/1, :61-71).  Filter i = filter_bytes[filter_offsets[i] ..
+ * filter_offsets[i+1]) with flag EMQXGM_RULE_EQ or 0, belonging to rule filter_rule[i]
+ * (non-decreasing, < n_rules; a rule with no filter never matches, :202-203).  Rule r has
+ * rule_perm[r] (EMQXGM_ACL_DENY | ALLOW), rule_action[r] (PUBLISH | SUBSCRIBE | ALL),
+ * rule_who[r] (EMQXGM_ACL_WHO_*), rule_slot[r] (< 64; read for WHO_HOST) and the who string
+ * who_bytes[who_offsets[r] .. who_offsets[r+1]) (read for WHO_USERNAME and WHO_CLIENTID).
+ * -EINVAL beyond the limits or on malformed offsets, flags, rule order, kinds or a slot of 64
+ * or more; the previous list then stays in force. */
+int emqxgm_acl_set(emqxgm_acl_t* a, const uint8_t* filter_bytes, const uint32_t* filter_offsets,
+                   const uint32_t* filter_flags, const uint32_t* filter_rule, uint32_t n_filters,
+                   const uint32_t* rule_perm, const uint32_t* rule_action, const uint32_t* rule_who,
+                   const uint32_t* rule_slot, const uint8_t* who_bytes, const uint32_t* who_offsets,
+                   uint32_t n_rules);
+/* matches/4 for a batch of requests: name i = bytes[offsets[i] .. offsets[i+1]) (a topic, or the
+ * filter of a subscribe, taken as words), client[i] an index into the call's client table,
+ * action[i] = EMQXGM_ACL_PUBLISH | SUBSCRIBE.  The client table: client ids and usernames as
+ * packed bytes + [n_clients+1] offsets, client_flags[c] (EMQXGM_ACL_NO_*: the value is undefined
+ * and its bytes are ignored), who_bits[c] (bit k set: client c satisfies host slot k).
+ * out_rule[i] = the first matching rule or EMQXGM_NONE.  -EINVAL, before anything is launched,
+ * on a client index out of range or an action other than publish or subscribe. */
+int emqxgm_acl_match(emqxgm_acl_t* a, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
+                     const uint32_t* client, const uint32_t* action, const uint8_t* clientid_bytes,
+                     const uint32_t* clientid_offsets, const uint8_t* username_bytes,
+                     const uint32_t* username_offsets, const uint32_t* client_flags,
+                     const uint64_t* who_bits, uint32_t n_clients, uint32_t* out_rule);
+/* "pass_names": requests per device pass (default 1 Mi); "counters": 1 = keep the four counters
+ * of emqxgm_acl_stats; "timing": 1 = HIP events around the kernel of every pass
+ * (tools/acl_bench.py), setting it clears the sum, which the read-only key "kernel_us" returns in
+ * microseconds (>= 0, the value is ignored) */
+int emqxgm_acl_tune(emqxgm_acl_t* a, const char* key, int64_t value);
+/* out = {filter records, record tiles, filters, rules, candidates sent to a byte check,
+ * candidates it removed, names deeper than 16 levels, records visited}; the last four since the
+ * last set */
+int emqxgm_acl_stats(emqxgm_acl_t* a, uint64_t out[8]);
 
 /* ---- single-driver batcher core: publish windows over the host pipes ---------------------
  * A caller that batches topics itself (one thread adding, flushing and collecting; bench.py's

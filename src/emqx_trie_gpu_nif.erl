@@ -39,7 +39,11 @@
     ruleset_open/2,
     ruleset_set/2,
     ruleset_match/2,
-    ruleset_close/1
+    ruleset_close/1,
+    acl_open/2,
+    acl_set/2,
+    acl_match/2,
+    acl_close/1
 ]).
 
 -on_load(init/0).
@@ -109,6 +113,18 @@ ruleset_set(_R, _Rules) -> ?NOT_LOADED.
 ruleset_match(_R, _Names) -> ?NOT_LOADED.
 %% ruleset_close(R) -> ok
 ruleset_close(_R) -> ?NOT_LOADED.
+%% ---- ACL lists: the first matching authz rule per request (emqx_authz_rule:matches/4 for
+%% emqx_authz_file:authorize/4 and emqx_authz_mnesia:authorize/4) ----
+%% acl_open(Device, WordHashBits :: 0) -> {ok, A} | {error, Reason}
+acl_open(_Device, _WordHashBits) -> ?NOT_LOADED.
+%% acl_set(A, [{allow | deny, Who, publish | subscribe | all, [{Filter, eq | words}]}]) -> ok:
+%% replaces the whole list; Who = all | {username, Bin} | {clientid, Bin} | {slot, 0..63}
+acl_set(_A, _Rules) -> ?NOT_LOADED.
+%% acl_match(A, {[{ClientId | undefined, Username | undefined, WhoBits}],
+%%               [{Name, ClientIndex, publish | subscribe}]}) -> [RuleIndex | none]
+acl_match(_A, _ClientsAndRequests) -> ?NOT_LOADED.
+%% acl_close(A) -> ok
+acl_close(_A) -> ?NOT_LOADED.
 %% snapshot_save(Res, Path :: binary()) -> ok | {error, Reason}: the committed index to a file
 snapshot_save(_Res, _Path) -> ?NOT_LOADED.
 %% snapshot_load(Res, Path :: binary()) -> ok | {error, Reason}: into a fresh resource, no build
