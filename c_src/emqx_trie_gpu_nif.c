@@ -1155,6 +1155,180 @@ static ERL_NIF_TERM nif_retain_match(ErlNifEnv* env, int argc, const ERL_NIF_TER
   return rc ? err_term(env, rc) : res;
 }
 
+/* ---- the rest of the retainer backend contract (emqx_retainer.erl:75-83) ---- */
+static ERL_NIF_TERM retain_topic_list(ErlNifEnv* env, gm_retain* g, const uint32_t* ids, uint64_t lo,
+                                      uint64_t hi) {
+  ERL_NIF_TERM tl = enif_make_list(env, 0);
+  for (uint64_t j = hi; j-- > lo;) {
+    const uint8_t* tp;
+    uint32_t tlen;
+    if (emqxgm_retain_topic(g->r, ids[j], &tp, &tlen) == 0)
+      tl = enif_make_list_cell(env, bytes_term(env, tp, tlen), tl);
+  }
+  return tl;
+}
+
+/* retain_store(R, Topic, ExpiryMs, TsMs) -> ok | {error, table_is_full}: store_retained/2 with the
+ * message timestamp (page_read's order) and the table-full rule (:141, max_retained_messages) */
+static ERL_NIF_TERM nif_retain_store_ts(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  ErlNifBinary b;
+  ErlNifUInt64 exp, ts;
+  uint32_t id;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &b) ||
+      !enif_get_uint64(env, argv[2], &exp) || !enif_get_uint64(env, argv[3], &ts))
+    return enif_make_badarg(env);
+  if (b.size > GM_MAX_TOPIC) return err_term(env, -E2BIG);
+  enif_mutex_lock(g->mu);
+  const int rc = emqxgm_retain_store_ts(g->r, b.data, (uint32_t)b.size, exp, ts, &id);
+  enif_mutex_unlock(g->mu);
+  if (rc == -ENOSPC)
+    return enif_make_tuple2(env, enif_make_atom(env, "error"), enif_make_atom(env, "table_is_full"));
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* retain_tune(R, Key :: atom(), Value) -> ok: delta_max | max_retained_messages */
+static ERL_NIF_TERM nif_retain_tune(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  char key[64];
+  ErlNifSInt64 v;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || enif_get_atom(env, argv[1], key, sizeof key, ERL_NIF_LATIN1) <= 0 ||
+      !enif_get_int64(env, argv[2], &v))
+    return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = emqxgm_retain_tune(g->r, key, v);
+  enif_mutex_unlock(g->mu);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* retain_match_limit(R, [Filter], NowMs, [Limit], [Cursor]) -> {[[Topic]], [Cursor]} |
+ * {error, Reason}: match_messages/3 with {Cursor, BatchNum} (:185-202) for a batch -- per filter
+ * its next Limit live topics (0: all) and the cursor to go on with.  A cursor is a 16-byte
+ * binary (emqxgm_retain_cursor in native layout; <<>> or 16 zero bytes start); its phase word
+ * is 3 when nothing remains and 4 when the store was rebuilt under it (restart that filter). */
+static ERL_NIF_TERM nif_retain_match_limit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  packed p;
+  ErlNifUInt64 now;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || !enif_get_uint64(env, argv[2], &now)) return enif_make_badarg(env);
+  int rc = pack_list(env, argv[1], 0, &p);
+  uint32_t* o = rc ? NULL : off32(&p);
+  if (!rc && !o) rc = -ENOMEM;
+  if (!rc && p.off[p.n] > 0xFFFFFFFFull) rc = -E2BIG;
+  uint32_t* lim = NULL;
+  emqxgm_retain_cursor* cur = NULL;
+  if (!rc) {
+    lim = enif_alloc(sizeof(uint32_t) * ((size_t)p.n + 1));
+    cur = enif_alloc(sizeof(emqxgm_retain_cursor) * ((size_t)p.n + 1));
+    if (!lim || !cur) rc = -ENOMEM;
+  }
+  if (!rc) {
+    ERL_NIF_TERM ll = argv[3], cl = argv[4], h;
+    for (unsigned i = 0; !rc && i < p.n; ++i) {
+      unsigned l;
+      ErlNifBinary cb;
+      if (!enif_get_list_cell(env, ll, &h, &ll) || !enif_get_uint(env, h, &l)) rc = -EINVAL;
+      lim[i] = l;
+      if (!rc && (!enif_get_list_cell(env, cl, &h, &cl) || !enif_inspect_binary(env, h, &cb) ||
+                  (cb.size != 0 && cb.size != sizeof(emqxgm_retain_cursor))))
+        rc = -EINVAL;
+      if (!rc) {
+        memset(&cur[i], 0, sizeof cur[i]);
+        if (cb.size) memcpy(&cur[i], cb.data, sizeof cur[i]);
+      }
+    }
+  }
+  emqxgm_retain_out out;
+  memset(&out, 0, sizeof out);
+  ERL_NIF_TERM res = 0;
+  if (!rc) {
+    enif_mutex_lock(g->mu); /* the result lives in the store's buffers until its next call */
+    rc = emqxgm_retain_match_limit(g->r, p.bytes, o, p.n, now, lim, cur, &out);
+    if (!rc) {
+      ERL_NIF_TERM rows = enif_make_list(env, 0), curs = enif_make_list(env, 0);
+      for (uint32_t i = out.n; i-- > 0;) {
+        ERL_NIF_TERM ct;
+        unsigned char* cp = enif_make_new_binary(env, sizeof(emqxgm_retain_cursor), &ct);
+        memcpy(cp, &cur[i], sizeof(emqxgm_retain_cursor));
+        curs = enif_make_list_cell(env, ct, curs);
+        rows = enif_make_list_cell(env, retain_topic_list(env, g, out.id, out.ptr[i], out.ptr[i + 1]), rows);
+      }
+      res = enif_make_tuple2(env, rows, curs);
+    }
+    enif_mutex_unlock(g->mu);
+  }
+  enif_free(cur);
+  enif_free(lim);
+  enif_free(o);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* retain_clear_expired(R, NowMs) -> [Topic]: clear_expired/1 (:154-164); the topics that left
+ * the store (committed) -- the caller deletes their messages */
+static ERL_NIF_TERM nif_retain_clear_expired(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  ErlNifUInt64 now;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || !enif_get_uint64(env, argv[1], &now)) return enif_make_badarg(env);
+  const uint32_t* ids = NULL;
+  uint64_t n = 0;
+  ERL_NIF_TERM res = 0;
+  enif_mutex_lock(g->mu);
+  const int rc = emqxgm_retain_clear_expired(g->r, now, &ids, &n);
+  if (!rc) res = retain_topic_list(env, g, ids, 0, n);
+  enif_mutex_unlock(g->mu);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* retain_delete_matching(R, Filter) -> [Topic]: delete_message/2 (:166-180), wildcards included;
+ * the topics deleted (committed) */
+static ERL_NIF_TERM nif_retain_delete_matching(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  ErlNifBinary b;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &b)) return enif_make_badarg(env);
+  if (b.size > GM_MAX_TOPIC) return enif_make_list(env, 0); /* never stored */
+  const uint32_t* ids = NULL;
+  uint64_t n = 0;
+  ERL_NIF_TERM res = 0;
+  enif_mutex_lock(g->mu);
+  const int rc = emqxgm_retain_delete_matching(g->r, b.data, (uint32_t)b.size, &ids, &n);
+  if (!rc) res = retain_topic_list(env, g, ids, 0, n);
+  enif_mutex_unlock(g->mu);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* retain_page_read(R, Filter | undefined, Page, Limit, NowMs) -> [Topic]: page_read/4 (:204-238),
+ * ordered by the timestamps given to retain_store/4 */
+static ERL_NIF_TERM nif_retain_page_read(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retain* g;
+  ErlNifBinary b;
+  ErlNifUInt64 page, limit, now;
+  (void)argc;
+  if (!get_retain(env, argv[0], &g) || !enif_get_uint64(env, argv[2], &page) ||
+      !enif_get_uint64(env, argv[3], &limit) || !enif_get_uint64(env, argv[4], &now))
+    return enif_make_badarg(env);
+  const int all = enif_is_atom(env, argv[1]);
+  if (!all && !enif_inspect_binary(env, argv[1], &b)) return enif_make_badarg(env);
+  if (!all && b.size > GM_MAX_TOPIC) return enif_make_list(env, 0);
+  const uint32_t* ids = NULL;
+  uint64_t n = 0;
+  ERL_NIF_TERM res = 0;
+  enif_mutex_lock(g->mu);
+  const int rc = emqxgm_retain_page_read(g->r, all ? NULL : b.data, all ? 0u : (uint32_t)b.size, page, limit,
+                                         now, &ids, &n);
+  if (!rc) res = retain_topic_list(env, g, ids, 0, n);
+  enif_mutex_unlock(g->mu);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
 /* match_rules(Res, [Name], [{Filter, eq | words | binary}]) -> [Index | none]: the first rule
  * each name matches (emqx_authz_rule:match_topics/3 with eq / words, emqx_rewrite's binary
  * match/2; placeholders substituted by the caller), on engine 0's device */
@@ -1701,6 +1875,12 @@ static ErlNifFunc funcs[] = {
     {"retain_clean", 1, nif_retain_clean, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"retain_commit", 1, nif_retain_commit, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"retain_match", 3, nif_retain_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"retain_store", 4, nif_retain_store_ts, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"retain_tune", 3, nif_retain_tune, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"retain_match_limit", 5, nif_retain_match_limit, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"retain_clear_expired", 2, nif_retain_clear_expired, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"retain_delete_matching", 2, nif_retain_delete_matching, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"retain_page_read", 5, nif_retain_page_read, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_rules", 3, nif_match_rules, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"ruleset_open", 2, nif_ruleset_open, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"ruleset_set", 2, nif_ruleset_set, ERL_NIF_DIRTY_JOB_IO_BOUND},

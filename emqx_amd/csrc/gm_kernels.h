@@ -231,6 +231,29 @@ hipError_t launch_retain_runs(const RetainDev& base, const RetainDev& delta, con
                               uint32_t* out, unsigned long long* total, bool fill, hipStream_t s);
 hipError_t launch_retain_ptr(const uint32_t* rbase, const uint32_t* abase, uint32_t n,
                              uint32_t* ptr, hipStream_t s);
+// Limited reads (emqxgm_retain_match_limit): the runs clipped to each filter's resume positions
+// rb / rd ([n], base / delta store).  Count: acnt = live ids per clipped run.  Fill: the first
+// win[f] live ids of filter f at out + wptr[f], and last[f] = {RUN_DELTA or 0, sorted position}
+// of the last one written.
+struct RetainWin {
+  const uint32_t* rbase = nullptr;  // [n+1]
+  uint32_t n = 0;
+  const uint32_t* rb = nullptr;
+  const uint32_t* rd = nullptr;
+  uint32_t* acnt = nullptr;         // [nr]
+  const uint32_t* abase = nullptr;  // [nr+1] (fill)
+  const uint32_t* win = nullptr;    // [n] (fill)
+  const uint32_t* wptr = nullptr;   // [n+1] (fill)
+  uint32_t* out = nullptr;
+  uint2* last = nullptr;            // [n]
+  unsigned long long* total = nullptr;  // count: += live ids of all clipped runs
+};
+hipError_t launch_retain_runs_win(const RetainDev& base, const RetainDev& delta, const uint2* runs,
+                                  uint32_t nr, uint64_t now, const RetainWin& w, bool fill,
+                                  hipStream_t s);
+// tot[f] = abase[rbase[f+1]] - abase[rbase[f]], win[f] = min(limit[f], tot[f]) (limit 0: tot)
+hipError_t launch_retain_win(const uint32_t* rbase, const uint32_t* abase, const uint32_t* limit,
+                             uint32_t n, uint32_t* tot, uint32_t* win, hipStream_t s);
 // Rule sets: every matching rule per name (gm_ruleset.inc / gm_ruleset.cpp), device pointers.
 // One pass of names against the resident list: a count launch (cnt), launch_ruleset_ptr (row =
 // exclusive scan of cnt, row[n] = total), a fill launch (rule[row[t] ..)).

@@ -1164,6 +1164,29 @@ hipError_t launch_retain_ptr(const uint32_t* rbase, const uint32_t* abase, uint3
   return hipGetLastError();
 }
 
+hipError_t launch_retain_runs_win(const RetainDev& base, const RetainDev& delta, const uint2* runs,
+                                  uint32_t nr, uint64_t now, const RetainWin& w, bool fill,
+                                  hipStream_t s) {
+  if (nr == 0 || w.n == 0) return hipSuccess;
+  RunWinArgs a{runs,     nr,        w.rbase,    w.n,       w.rb,   w.rd,    base.sexp, base.sid,
+               delta.sexp, delta.sid, now,      w.acnt,    w.abase, w.win,  w.wptr,    w.out,
+               w.last,   w.total};
+  const dim3 grid(grid_for((uint64_t)nr * 64, 8192));
+  if (fill)
+    hipLaunchKernelGGL(k_retain_runs_win<true>, grid, dim3(WG), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_retain_runs_win<false>, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_retain_win(const uint32_t* rbase, const uint32_t* abase, const uint32_t* limit,
+                             uint32_t n, uint32_t* tot, uint32_t* win, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_retain_win, dim3((n + WG - 1) / WG), dim3(WG), 0, s, rbase, abase, limit, n,
+                     tot, win);
+  return hipGetLastError();
+}
+
 hipError_t launch_ruleset(const RulesetArgs& a, bool fill, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));

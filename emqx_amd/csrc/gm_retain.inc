@@ -192,3 +192,142 @@ __global__ __launch_bounds__(WG) void k_retain_ptr(const uint32_t* rbase, const 
   const uint32_t f = blockIdx.x * WG + threadIdx.x;
   if (f <= n) ptr[f] = abase[rbase[f]];
 }
+
+// ---- limited reads (emqxgm_retain_match_limit): a window of each filter's ids ----
+// The dispatcher reads retained messages batch_read_number at a time through a cursor
+// (emqx_retainer_mnesia.erl:185-202, qlc_next_answers/2 :384-397).  The walk produces the runs
+// as for the unlimited match; k_retain_runs_win then looks only at the part of each run at or
+// after its filter's resume position (host-computed from the cursor: rb[f] in the base store,
+// rd[f] in the delta store; the store's size skips the store), and the fill pass writes only
+// the first win[f] live ids of filter f.  A live id's rank in its filter is its global rank
+// (abase) minus abase[rbase[f]], so the walk needs no output beyond the runs.
+//
+// Written as per-lane functions with the wave's ballot between them (rw_open, rw_live, rw_put):
+// the kernel below is their only device caller, and the host harness
+// (tests/host_harness/retain_dev_main.cpp) runs the same functions for lanes 0 .. 63 in turn
+// with the ballot computed between the phases.
+
+struct RunWinArgs {
+  const uint2* runs;
+  uint32_t nr;
+  const uint32_t* rbase;  // [n+1] first run of each filter
+  uint32_t n;
+  const uint32_t* rb;     // [n] resume position in the base store
+  const uint32_t* rd;     // [n] resume position in the delta store
+  const uint64_t* sexp0;  // base store
+  const uint32_t* sid0;
+  const uint64_t* sexp1;  // delta store
+  const uint32_t* sid1;
+  uint64_t now;
+  uint32_t* acnt;         // [nr] live ids of each clipped run (count pass)
+  const uint32_t* abase;  // [nr+1] scanned acnt (fill pass)
+  const uint32_t* win;    // [n] ids to write per filter (fill pass)
+  const uint32_t* wptr;   // [n+1] scanned win: the output rows
+  uint32_t* out;
+  uint2* last;            // [n] {RUN_DELTA or 0, sorted position} of the id of rank win - 1
+  unsigned long long* total;  // count pass: live ids of all clipped runs (the ranks are 32-bit)
+};
+
+// One clipped run as its wave sees it (the same in every lane).
+struct RwRun {
+  const uint64_t* sexp;
+  const uint32_t* sid;
+  uint32_t f;     // the run's filter
+  uint32_t tag;   // RUN_DELTA or 0
+  uint32_t lo, hi;  // clipped positions [lo, hi)
+  uint32_t rank;  // fill: rank in the filter of the run's first live id
+  uint32_t w;     // fill: the filter's window
+};
+
+// The filter of run r: the last f with rbase[f] <= r (filters without runs repeat their
+// neighbour's rbase and are passed over).  r < rbase[n].
+__device__ __forceinline__ uint32_t rw_filter(const uint32_t* rbase, uint32_t n, uint32_t r) {
+  uint32_t lo = 0, hi = n;  // rbase[lo] <= r < rbase[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (rbase[mid] <= r)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+template <bool FILL>
+__device__ __forceinline__ RwRun rw_open(const RunWinArgs& A, uint32_t r) {
+  RwRun R;
+  const uint2 run = A.runs[r];
+  R.f = rw_filter(A.rbase, A.n, r);
+  R.tag = run.x & RUN_DELTA;
+  R.sexp = R.tag ? A.sexp1 : A.sexp0;
+  R.sid = R.tag ? A.sid1 : A.sid0;
+  const uint32_t from = R.tag ? A.rd[R.f] : A.rb[R.f];
+  R.lo = run.x & ~RUN_DELTA;
+  if (R.lo < from) R.lo = from;
+  R.hi = run.y;
+  R.rank = 0;
+  R.w = 0;
+  if (FILL) {
+    R.rank = A.abase[r] - A.abase[A.rbase[R.f]];
+    R.w = A.win[R.f];
+  }
+  return R;
+}
+
+// Is position i of the run a live topic (one coalesced 8-byte load per lane)?
+__device__ __forceinline__ bool rw_live(const RwRun& R, uint32_t i, uint64_t now) {
+  if (i >= R.hi) return false;
+  const uint64_t e = R.sexp[i];
+  return e != RDEAD && (e == 0 || e > now);
+}
+
+// Fill: a live lane whose rank is inside the window writes its id; the window's last rank
+// also leaves where it was found.
+__device__ __forceinline__ void rw_put(const RunWinArgs& A, const RwRun& R, uint32_t i, bool live,
+                                       uint32_t rank) {
+  if (!live || rank >= R.w) return;
+  A.out[A.wptr[R.f] + rank] = R.sid[i];
+  if (rank + 1 == R.w) A.last[R.f] = make_uint2(R.tag, i);
+}
+
+// One wave per run, as k_retain_runs.
+template <bool FILL>
+__global__ __launch_bounds__(WG) void k_retain_runs_win(RunWinArgs A) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * WG + threadIdx.x) >> 6;
+  const uint32_t nw = (gridDim.x * WG) >> 6;
+  for (uint32_t r = wave; r < A.nr; r += nw) {
+    RwRun R = rw_open<FILL>(A, r);
+    if (FILL && R.rank >= R.w) continue;  // past the window: no expiry word is read
+    uint32_t c = 0;
+    for (uint32_t b = R.lo; b < R.hi; b += 64) {
+      const uint32_t i = b + lane;
+      const bool live = rw_live(R, i, A.now);
+      const uint64_t m = __ballot(live);
+      if (FILL) rw_put(A, R, i, live, R.rank + c + __popcll(m & ((1ull << lane) - 1)));
+      c += __popcll(m);
+      if (FILL && R.rank + c >= R.w) break;
+    }
+    if (!FILL && lane == 0) {
+      A.acnt[r] = c;
+      atomicAdd(A.total, (unsigned long long)c);
+    }
+  }
+}
+
+// Per filter: tot = live ids at or after its cursor, win = min(limit, tot) (limit 0: all).
+__device__ __forceinline__ void rw_window(const uint32_t* rbase, const uint32_t* abase,
+                                          const uint32_t* limit, uint32_t f, uint32_t* tot,
+                                          uint32_t* win) {
+  const uint32_t t = abase[rbase[f + 1]] - abase[rbase[f]];
+  const uint32_t l = limit[f];
+  tot[f] = t;
+  win[f] = (l != 0 && l < t) ? l : t;
+}
+
+__global__ __launch_bounds__(WG) void k_retain_win(const uint32_t* rbase, const uint32_t* abase,
+                                                   const uint32_t* limit, uint32_t n, uint32_t* tot,
+                                                   uint32_t* win) {
+  const uint32_t f = blockIdx.x * WG + threadIdx.x;
+  if (f < n) rw_window(rbase, abase, limit, f, tot, win);
+}

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 7  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 8  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -210,6 +210,14 @@ SYMBOLS = {
     "emqxgm_retain_read": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),
     "emqxgm_retain_topic": (C.c_int, [_P, C.c_uint32, C.POINTER(_U8P), _U32P]),
     "emqxgm_retain_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, C.POINTER(_RetOut)]),
+    "emqxgm_retain_match_limit": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, _P, _P,
+                                            C.POINTER(_RetOut)]),
+    "emqxgm_retain_timing": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "emqxgm_retain_store_ts": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64, _U32P]),
+    "emqxgm_retain_clear_expired": (C.c_int, [_P, C.c_uint64, C.POINTER(_U32P), _U64P]),
+    "emqxgm_retain_delete_matching": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(_U32P), _U64P]),
+    "emqxgm_retain_page_read": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64,
+                                          C.c_uint64, C.POINTER(_U32P), _U64P]),
     "emqxgm_ruleset_create": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(_P)]),
     "emqxgm_ruleset_destroy": (None, [_P]),
     "emqxgm_ruleset_set": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32]),

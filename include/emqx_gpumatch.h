@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 7
+#define EMQXGM_ABI_VERSION 8
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -418,7 +418,9 @@ int emqxgm_retain_clean(emqxgm_retain_t* r); /* clean/1 (:241-244) */
 int emqxgm_retain_commit(emqxgm_retain_t* r);
 /* Committed state = a base store plus a small delta store of the topics stored since the base
  * was built; re-storing or deleting a base topic patches it in place.  "delta_max": delta topics
- * before a commit rebuilds the base (-1 = max(4096, base / 16), 0 = rebuild at every commit). */
+ * before a commit rebuilds the base (-1 = max(4096, base / 16), 0 = rebuild at every commit).
+ * "max_retained_messages": the table-full limit of emqxgm_retain_store_ts (0 = none).
+ * "timing": see emqxgm_retain_timing. */
 int emqxgm_retain_tune(emqxgm_retain_t* r, const char* key, int64_t value);
 /* The retainer's index specs (retainer.backend.index_specs, config_indices/0 of
  * emqx_retainer_mnesia.erl:424-425): spec i = positions pos[offsets[i] .. offsets[i+1]), each
@@ -445,6 +447,67 @@ typedef struct emqxgm_retain_out { /* host-resident, valid until the next call o
 /* match_messages/3 for a batch of filters (packed bytes + [n+1] offsets on the host) */
 int emqxgm_retain_match(emqxgm_retain_t* r, const uint8_t* bytes, const uint32_t* offsets,
                         uint32_t n, uint64_t now_ms, emqxgm_retain_out* out);
+
+/* match_messages/3 with {Cursor, BatchNum} (:185-202, qlc_next_answers/2 :384-397): the
+ * dispatcher's flow control (emqx_retainer_dispatcher.erl:242-257) reads batch_read_number
+ * messages at a time.  A filter's ids come in emqxgm_retain_match's order (base topics in word
+ * order, then delta topics in word order); a call returns, per filter, the first limit[i] live
+ * ids at or after cur[i] (limit 0: all of them) and advances cur[i].  Only the windows are
+ * computed into the output and downloaded.
+ *  * A zeroed cursor starts.  phase becomes DONE when nothing live remains after the window at
+ *    this call -- one call earlier than qlc_next_answers/2 reports `closed` when exactly N
+ *    answers remain (it then needs one more, empty, read); the rows delivered are the same.
+ *    An entry that comes in DONE or STALE yields an empty row and stays as it is.
+ *  * A cursor belongs to one base generation (gen = full rebuilds at its first call): base
+ *    positions are stable while the base is only patched.  After a full rebuild or a clean the
+ *    entry comes back STALE with an empty row and the caller restarts that filter; the other
+ *    entries proceed and the call returns 0.  A delta cursor resumes by bytes: after the topic
+ *    `at` in the current delta store's word order, whether or not it is still stored.
+ *  * While no full rebuild intervenes, a topic that is selected and untouched from the first
+ *    page to the last is returned exactly once; no topic is returned twice; a topic stored
+ *    meanwhile may or may not be seen -- what a qlc cursor over a fixed ets table gives.
+ *  * -EINVAL, before anything is launched: an unknown phase, a BASE cursor with `at` past the
+ *    base store's size, a DELTA cursor whose `at` is no topic id.  -E2BIG: the windows together
+ *    hold 2^32 ids or more, or (ranks are 32-bit) so many live ids remain after the cursors. */
+enum { EMQXGM_RC_START = 0, EMQXGM_RC_BASE = 1, EMQXGM_RC_DELTA = 2, EMQXGM_RC_DONE = 3,
+       EMQXGM_RC_STALE = 4 };
+typedef struct emqxgm_retain_cursor {
+  uint64_t gen;   /* base generation the cursor belongs to */
+  uint32_t phase; /* EMQXGM_RC_* */
+  uint32_t at;    /* BASE: next sorted position of the base store;
+                     DELTA: id of the last delta topic returned */
+} emqxgm_retain_cursor;
+int emqxgm_retain_match_limit(emqxgm_retain_t* r, const uint8_t* bytes, const uint32_t* offsets,
+                              uint32_t n, uint64_t now_ms, const uint32_t* limit /* [n], 0 = all */,
+                              emqxgm_retain_cursor* cur /* [n], in/out, zeroed = start */,
+                              emqxgm_retain_out* out);
+/* With emqxgm_retain_tune "timing" = 1: HIP-event times in ms of the last
+ * emqxgm_retain_match_limit's own launches -- {count pass of k_retain_runs_win, the scans and
+ * k_retain_win between the passes (two host round trips included), fill pass}. */
+int emqxgm_retain_timing(emqxgm_retain_t* r, double out[3]);
+/* store_retained/2 with #message.timestamp (kept in the host registry, for page_read);
+ * emqxgm_retain_store is this call with ts_ms = 0.  With emqxgm_retain_tune
+ * "max_retained_messages" = L > 0 (is_table_full/0 and is_new_topic/1, :141, :409-419): a topic
+ * that is not stored, while L or more are (expired but uncleared ones count, table_size/0),
+ * returns -ENOSPC and changes nothing; storing a stored topic again always succeeds.  0: no limit. */
+int emqxgm_retain_store_ts(emqxgm_retain_t* r, const uint8_t* topic, uint32_t len,
+                           uint64_t expiry_ms, uint64_t ts_ms, uint32_t* id);
+/* clear_expired/1 (:154-164): deletes every stored topic with expiry != 0 and expiry < now_ms
+ * (strictly, :161; the match keeps > now, the read >= now), commits, and returns their ids
+ * (valid until the next call on r): the caller deletes those messages from its own table. */
+int emqxgm_retain_clear_expired(emqxgm_retain_t* r, uint64_t now_ms, const uint32_t** ids,
+                                uint64_t* n);
+/* delete_message/2 (:166-180): commits pending changes; a wildcard filter deletes every topic
+ * search_table(Tokens, 0) selects (:172), any other the topic itself; commits; returns the ids
+ * deleted (valid until the next call on r). */
+int emqxgm_retain_delete_matching(emqxgm_retain_t* r, const uint8_t* filter, uint32_t len,
+                                  const uint32_t** ids, uint64_t* n);
+/* page_read/4 (:204-238), the dashboard listing: commits; filter NULL = '#' on the full scan
+ * (search_table(undefined, ['#'], Now), :209), else the filter through the configured indices;
+ * the selected ids in a stable sort by timestamp (compare_message/2, :364-365), entries
+ * [(page-1)*limit, page*limit) of them.  page = 0 or limit = 0: -EINVAL.  Host sort. */
+int emqxgm_retain_page_read(emqxgm_retain_t* r, const uint8_t* filter, uint32_t len, uint64_t page,
+                            uint64_t limit, uint64_t now_ms, const uint32_t** ids, uint64_t* n);
 
 /* ---- rule sets: every matching rule per name, against a resident list ----
  * The loops that keep every match, run once per publish beside the route match:

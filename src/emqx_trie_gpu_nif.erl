@@ -35,6 +35,12 @@
     retain_clean/1,
     retain_commit/1,
     retain_match/3,
+    retain_store/4,
+    retain_tune/3,
+    retain_match_limit/5,
+    retain_clear_expired/2,
+    retain_delete_matching/2,
+    retain_page_read/5,
     match_rules/3,
     ruleset_open/2,
     ruleset_set/2,
@@ -100,6 +106,20 @@ retain_clean(_R) -> ?NOT_LOADED.
 retain_commit(_R) -> ?NOT_LOADED.
 %% retain_match(R, [Filter], NowMs) -> [[Topic]]: match_messages/3 for a batch of filters
 retain_match(_R, _Filters, _NowMs) -> ?NOT_LOADED.
+%% retain_store(R, Topic, ExpiryMs, TsMs) -> ok | {error, table_is_full}: store_retained/2 with
+%% #message.timestamp and the table-full rule (emqx_retainer_mnesia.erl:141, :409-419)
+retain_store(_R, _Topic, _ExpiryMs, _TsMs) -> ?NOT_LOADED.
+%% retain_tune(R, delta_max | max_retained_messages, Value) -> ok
+retain_tune(_R, _Key, _Value) -> ?NOT_LOADED.
+%% retain_match_limit(R, [Filter], NowMs, [Limit], [Cursor]) -> {[[Topic]], [Cursor]}:
+%% match_messages/3 with {Cursor, BatchNum} (:185-202); a cursor is a 16-byte binary, <<>> starts
+retain_match_limit(_R, _Filters, _NowMs, _Limits, _Cursors) -> ?NOT_LOADED.
+%% retain_clear_expired(R, NowMs) -> [Topic] (clear_expired/1, :154-164)
+retain_clear_expired(_R, _NowMs) -> ?NOT_LOADED.
+%% retain_delete_matching(R, Filter) -> [Topic] (delete_message/2 with wildcards, :166-180)
+retain_delete_matching(_R, _Filter) -> ?NOT_LOADED.
+%% retain_page_read(R, Filter | undefined, Page, Limit, NowMs) -> [Topic] (page_read/4, :204-238)
+retain_page_read(_R, _Filter, _Page, _Limit, _NowMs) -> ?NOT_LOADED.
 %% match_rules(Res, [Name], [{Filter, eq | words | binary}]) -> [Index | none]: the first rule
 %% each name matches (emqx_authz_rule:match_topics/3, emqx_rewrite:match_and_rewrite/3)
 match_rules(_Res, _Names, _Rules) -> ?NOT_LOADED.
