@@ -72,10 +72,10 @@ typedef struct {
   int publish;
 } gm_call;
 
-static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT, *ACL_RT;
+static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT, *ACL_RT, *ACLDB_RT;
 static ERL_NIF_TERM A_OK, A_ERROR, A_TRUE, A_FALSE, A_MOD, A_ROUTES, A_NONE, A_NODE, A_GROUP, A_SUB,
     A_SPIN_US, A_BG_BUILD, A_PUBLISH, A_UNDEFINED, A_REPORT_THREADS, A_EQ, A_WORDS, A_BINARY,
-    A_FAIL_THRESHOLD, A_EAGER, A_ALLOW, A_DENY, A_SUBSCRIBE, A_ALL, A_USERNAME, A_CLIENTID, A_SLOT;
+    A_FAIL_THRESHOLD, A_EAGER, A_ALLOW, A_DENY, A_SUBSCRIBE, A_ALL, A_USERNAME, A_CLIENTID, A_SLOT, A_NOMATCH;
 
 static int tab_init(term_tab* t, char* name) {
   t->lk = enif_rwlock_create(name);
@@ -1803,6 +1803,228 @@ static ERL_NIF_TERM nif_acl_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM a
   return A_OK;
 }
 
+/* ---- the built-in authorization database, keyed by client ---------------------------------------
+ * emqx_authz_mnesia (emqx_authz_mnesia.erl): store_rules/2, delete_rules/1 and purge_rules/0
+ * (:132-169) are mirrored into an emqxgm_acldb_t, made visible by acldb_commit/1, and
+ * acldb_match/2 answers authorize/4 (:98-120) per request: the permission, the record that decided
+ * (clientid | username | all) and the rule's position in it, or nomatch.  emqx_access_control's
+ * no_match default stays with the caller. */
+typedef struct {
+  emqxgm_acldb_t* d; /* NULL once closed */
+  ErlNifMutex* mu;
+} gm_acldb;
+
+static void gm_acldb_dtor(ErlNifEnv* env, void* obj) {
+  gm_acldb* g = (gm_acldb*)obj;
+  (void)env;
+  if (g->d) emqxgm_acldb_destroy(g->d);
+  if (g->mu) enif_mutex_destroy(g->mu);
+}
+
+static int get_acldb(ErlNifEnv* env, ERL_NIF_TERM t, gm_acldb** g) {
+  return enif_get_resource(env, t, ACLDB_RT, (void**)g) && (*g)->mu;
+}
+
+/* clientid | username | all -> EMQXGM_ACLDB_* */
+static int acldb_kind(ERL_NIF_TERM t, uint32_t* kind) {
+  if (t == A_CLIENTID) *kind = EMQXGM_ACLDB_CLIENTID;
+  else if (t == A_USERNAME) *kind = EMQXGM_ACLDB_USERNAME;
+  else if (t == A_ALL) *kind = EMQXGM_ACLDB_ALL;
+  else return 0;
+  return 1;
+}
+
+/* acldb_open(Device, WordHashBits) -> {ok, D} | {error, Reason} (WordHashBits: 0 but in tests) */
+static ERL_NIF_TERM nif_acldb_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  int dev;
+  unsigned bits;
+  (void)argc;
+  if (!enif_get_int(env, argv[0], &dev) || !enif_get_uint(env, argv[1], &bits)) return enif_make_badarg(env);
+  gm_acldb* g = enif_alloc_resource(ACLDB_RT, sizeof(gm_acldb));
+  memset(g, 0, sizeof *g);
+  g->mu = enif_mutex_create("emqx_trie_gpu.acldb");
+  const int rc = g->mu ? emqxgm_acldb_create(dev, bits, &g->d) : -ENOMEM;
+  if (rc) {
+    enif_release_resource(g);
+    return rc == -EINVAL ? enif_make_badarg(env) : err_term(env, rc);
+  }
+  ERL_NIF_TERM t = enif_make_resource(env, g);
+  enif_release_resource(g);
+  return enif_make_tuple2(env, A_OK, t);
+}
+
+/* acldb_store(D, clientid | username | all, Key, [{allow | deny, publish | subscribe | all, Topic}])
+ * -> ok | {error, Reason}: store_rules/2, pending until acldb_commit/1.  Key and Topic are
+ * binaries (the key is ignored for all); a topic "eq T" is {eq, T}.  badarg on a malformed rule
+ * (normalize_rules/1, :195-214, is the caller's); the record in force stays. */
+static ERL_NIF_TERM nif_acldb_store(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acldb* g;
+  uint32_t kind;
+  ErlNifBinary key;
+  unsigned nr;
+  (void)argc;
+  if (!get_acldb(env, argv[0], &g) || !acldb_kind(argv[1], &kind) || !enif_inspect_binary(env, argv[2], &key) ||
+      key.size > 0xFFFFFFFFull || !enif_get_list_length(env, argv[3], &nr))
+    return enif_make_badarg(env);
+  const size_t rn = nr ? nr : 1;
+  uint32_t* ru = enif_alloc(sizeof(uint32_t) * rn * 3); /* perm, action, "topic is undefined" */
+  packed_opt tp;
+  memset(&tp, 0, sizeof tp);
+  int rc = ru ? 0 : -ENOMEM;
+  if (!rc) {
+    memset(ru, 0, sizeof(uint32_t) * rn * 3);
+    rc = pack_opt(env, argv[3], nr, 2, ru + 2 * rn, 1u, &tp);
+  }
+  ERL_NIF_TERM head, l = argv[3];
+  for (unsigned i = 0; !rc && i < nr; ++i) {
+    int ar;
+    const ERL_NIF_TERM* el;
+    enif_get_list_cell(env, l, &head, &l);
+    enif_get_tuple(env, head, &ar, &el);
+    if (ar != 3 || ru[2 * rn + i]) rc = -EINVAL;
+    else if (el[0] == A_ALLOW) ru[i] = EMQXGM_ACL_ALLOW;
+    else if (el[0] == A_DENY) ru[i] = EMQXGM_ACL_DENY;
+    else rc = -EINVAL;
+    if (rc) break;
+    if (el[1] == A_PUBLISH) ru[rn + i] = EMQXGM_ACL_PUBLISH;
+    else if (el[1] == A_SUBSCRIBE) ru[rn + i] = EMQXGM_ACL_SUBSCRIBE;
+    else if (el[1] == A_ALL) ru[rn + i] = EMQXGM_ACL_ALL;
+    else rc = -EINVAL;
+  }
+  if (!rc) {
+    enif_mutex_lock(g->mu);
+    rc = g->d ? emqxgm_acldb_store(g->d, kind, key.data, (uint32_t)key.size, ru, ru + rn, tp.bytes, tp.off, nr)
+              : -EINVAL;
+    enif_mutex_unlock(g->mu);
+  }
+  enif_free(ru);
+  packed_opt_free(&tp);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* acldb_delete(D, clientid | username | all, Key) -> ok: delete_rules/1, pending until the commit */
+static ERL_NIF_TERM nif_acldb_delete(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acldb* g;
+  uint32_t kind;
+  ErlNifBinary key;
+  (void)argc;
+  if (!get_acldb(env, argv[0], &g) || !acldb_kind(argv[1], &kind) || !enif_inspect_binary(env, argv[2], &key) ||
+      key.size > 0xFFFFFFFFull)
+    return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->d ? emqxgm_acldb_delete(g->d, kind, key.data, (uint32_t)key.size) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* acldb_purge(D) -> ok (purge_rules/0) and acldb_commit(D) -> ok | {error, Reason} */
+static ERL_NIF_TERM acldb_call(ErlNifEnv* env, ERL_NIF_TERM h, int (*fn)(emqxgm_acldb_t*)) {
+  gm_acldb* g;
+  if (!get_acldb(env, h, &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->d ? fn(g->d) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+static ERL_NIF_TERM nif_acldb_purge(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return acldb_call(env, argv[0], emqxgm_acldb_purge);
+}
+
+static ERL_NIF_TERM nif_acldb_commit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return acldb_call(env, argv[0], emqxgm_acldb_commit);
+}
+
+/* acldb_match(D, {[{ClientId | undefined, Username | undefined}],
+ *                 [{Name, ClientIndex, publish | subscribe}]}) ->
+ *     [{allow | deny, clientid | username | all, Position} | nomatch] | {error, Reason}:
+ * authorize/4 per request; ClientIndex (from 0) points into the call's client list. */
+static ERL_NIF_TERM nif_acldb_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acldb* g;
+  int ar;
+  const ERL_NIF_TERM* arg;
+  unsigned nc;
+  (void)argc;
+  if (!get_acldb(env, argv[0], &g) || !enif_get_tuple(env, argv[1], &ar, &arg) || ar != 2 ||
+      !enif_get_list_length(env, arg[0], &nc))
+    return enif_make_badarg(env);
+  packed p;
+  packed_opt ci, us;
+  memset(&ci, 0, sizeof ci);
+  memset(&us, 0, sizeof us);
+  int rc = pack_list(env, arg[1], 1, &p);
+  const size_t cn = nc ? nc : 1, rn = p.n ? p.n : 1;
+  uint32_t* o = rc ? NULL : off32(&p);
+  uint32_t* cf = enif_alloc(sizeof(uint32_t) * cn);
+  uint32_t* rq = rc ? NULL : enif_alloc(sizeof(uint32_t) * rn * 5); /* client, action, perm, src, pos */
+  if (!rc && (!o || !cf || !rq)) rc = -ENOMEM;
+  if (!rc && p.off[p.n] > 0xFFFFFFFFull) rc = -E2BIG;
+  if (!rc) {
+    memset(cf, 0, sizeof(uint32_t) * cn);
+    rc = pack_opt(env, arg[0], nc, 0, cf, EMQXGM_ACL_NO_CLIENTID, &ci);
+  }
+  if (!rc) rc = pack_opt(env, arg[0], nc, 1, cf, EMQXGM_ACL_NO_USERNAME, &us);
+  ERL_NIF_TERM head, l = arg[1];
+  for (unsigned i = 0; !rc && i < p.n; ++i) {
+    const ERL_NIF_TERM* el;
+    unsigned c;
+    enif_get_list_cell(env, l, &head, &l);
+    enif_get_tuple(env, head, &ar, &el);
+    if (ar != 3 || !enif_get_uint(env, el[1], &c)) rc = -EINVAL;
+    else if (el[2] == A_PUBLISH) rq[rn + i] = EMQXGM_ACL_PUBLISH;
+    else if (el[2] == A_SUBSCRIBE) rq[rn + i] = EMQXGM_ACL_SUBSCRIBE;
+    else rc = -EINVAL;
+    if (!rc) rq[i] = c;
+  }
+  ERL_NIF_TERM res = 0;
+  if (!rc) {
+    uint32_t *perm = rq + 2 * rn, *src = rq + 3 * rn, *pos = rq + 4 * rn;
+    enif_mutex_lock(g->mu);
+    rc = g->d ? emqxgm_acldb_match(g->d, p.bytes, o, p.n, rq, rq + rn, ci.bytes, ci.off, us.bytes, us.off, cf, nc,
+                                   perm, src, pos)
+              : -EINVAL;
+    enif_mutex_unlock(g->mu);
+    if (!rc) {
+      res = enif_make_list(env, 0);
+      for (uint32_t i = p.n; i-- > 0;) {
+        ERL_NIF_TERM t = A_NOMATCH;
+        if (perm[i] != EMQXGM_NONE)
+          t = enif_make_tuple3(env, perm[i] == EMQXGM_ACL_ALLOW ? A_ALLOW : A_DENY,
+                               src[i] == EMQXGM_ACLDB_CLIENTID   ? A_CLIENTID
+                               : src[i] == EMQXGM_ACLDB_USERNAME ? A_USERNAME
+                                                                 : A_ALL,
+                               enif_make_uint(env, pos[i]));
+        res = enif_make_list_cell(env, t, res);
+      }
+    }
+  }
+  enif_free(o);
+  enif_free(cf);
+  enif_free(rq);
+  packed_opt_free(&ci);
+  packed_opt_free(&us);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* acldb_close(D) -> ok: frees the device database now (the resource's destructor otherwise) */
+static ERL_NIF_TERM nif_acldb_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_acldb* g;
+  (void)argc;
+  if (!get_acldb(env, argv[0], &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  if (g->d) emqxgm_acldb_destroy(g->d);
+  g->d = NULL;
+  enif_mutex_unlock(g->mu);
+  return A_OK;
+}
+
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
@@ -1811,7 +2033,9 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   RETAIN_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_retain", gm_retain_dtor, ERL_NIF_RT_CREATE, NULL);
   RULESET_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_ruleset", gm_ruleset_dtor, ERL_NIF_RT_CREATE, NULL);
   ACL_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_acl", gm_acl_dtor, ERL_NIF_RT_CREATE, NULL);
-  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || !ACL_RT || emqxgm_abi_version() != EMQXGM_ABI_VERSION)
+  ACLDB_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_acldb", gm_acldb_dtor, ERL_NIF_RT_CREATE, NULL);
+  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || !ACL_RT || !ACLDB_RT ||
+      emqxgm_abi_version() != EMQXGM_ABI_VERSION)
     return -1;
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
@@ -1839,6 +2063,7 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   A_ALL = enif_make_atom(env, "all");
   A_USERNAME = enif_make_atom(env, "username");
   A_CLIENTID = enif_make_atom(env, "clientid");
+  A_NOMATCH = enif_make_atom(env, "nomatch");
   A_SLOT = enif_make_atom(env, "slot");
   return 0;
 }
@@ -1890,6 +2115,13 @@ static ErlNifFunc funcs[] = {
     {"acl_set", 2, nif_acl_set, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acl_match", 2, nif_acl_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acl_close", 1, nif_acl_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_open", 2, nif_acldb_open, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_store", 4, nif_acldb_store, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_delete", 3, nif_acldb_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_purge", 1, nif_acldb_purge, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_commit", 1, nif_acldb_commit, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_match", 2, nif_acldb_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acldb_close", 1, nif_acldb_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(emqx_trie_gpu_nif, funcs, load, NULL, NULL, NULL)

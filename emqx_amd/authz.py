@@ -264,3 +264,124 @@ class AclList:
         emqx_authz_mnesia:authorize/4's ``clientid ++ username ++ all`` order (:98-120), each rule
         compiled as ``{Permission, all, Action, [TopicFilter]}`` (:222-229)."""
         return cls(cls.builtin_db_rules(records), **kw)
+
+
+class InvalidRule(ValueError):
+    """normalize_rules/1's errors (emqx_authz_mnesia.erl:195-214): ``reason`` is one of
+    ``invalid_rule``, ``invalid_rule_permission``, ``invalid_rule_action``, ``invalid_rule_topic``."""
+
+    def __init__(self, reason: str, term):
+        super().__init__(f"{reason}: {term!r}")
+        self.reason, self.term = reason, term
+
+
+def normalize_rules(rules) -> list:
+    """normalize_rules/1 (:195-214): ``[(permission, action, topic)]`` with the atoms as ``str`` and
+    the topic a string (``str``) or a binary (``bytes``) -> the same with every topic ``bytes``."""
+    out = []
+    for rule in rules:
+        if not isinstance(rule, tuple) or len(rule) != 3:
+            raise InvalidRule("invalid_rule", rule)
+        perm, action, topic = rule
+        if not isinstance(perm, str) or perm not in _PERMS:
+            raise InvalidRule("invalid_rule_permission", perm)
+        if not isinstance(action, str) or action not in _ACTIONS:
+            raise InvalidRule("invalid_rule_action", action)
+        if not isinstance(topic, (str, bytes, bytearray)):
+            raise InvalidRule("invalid_rule_topic", topic)
+        out.append((perm, action, _bin(topic)))
+    return out
+
+
+class BuiltinDb:
+    """The built-in database resident on the device (DESIGN.md 6b "Built-in database"): the mirror
+    of ``emqx_authz_mnesia`` (apps/emqx_authz/src/emqx_authz_mnesia.erl) over ``emqx_amd.AclDb``.
+    ``who`` is ``("clientid", C)``, ``("username", U)`` or ``"all"`` (:41-58).  Mutations are
+    pending until ``commit()``; ``authorize`` answers from the committed records, ``get_rules`` and
+    ``record_count`` tell what is stored, pending mutations included."""
+
+    def __init__(self, device: int = 0, word_hash_bits: int = 0):
+        self.db = E.AclDb(device=device, word_hash_bits=word_hash_bits)
+        self.records: Dict[object, list] = {}
+
+    def close(self):
+        self.db.close()
+
+    @staticmethod
+    def _who(who):
+        if who == "all":
+            return "all", E.ACLDB_ALL, b""
+        kind, value = who
+        kind = _atom(kind)
+        if kind not in ("clientid", "username"):
+            raise ValueError(f"unknown key {who!r}")
+        value = _bin(value)
+        return (kind, value), (E.ACLDB_CLIENTID if kind == "clientid" else E.ACLDB_USERNAME), value
+
+    @staticmethod
+    def _numbers(rules):
+        return [(_PERMS[p], _ACTIONS[a], t) for p, a, t in rules]
+
+    def store_rules(self, who, rules) -> None:
+        """store_rules/2 (:132-150): replaces the record."""
+        key, kind, value = self._who(who)
+        rules = normalize_rules(rules)
+        self.db.store(kind, value, self._numbers(rules))
+        self.records[key] = rules
+
+    def store_many(self, records) -> None:
+        """store_rules/2 for ``[(who, rules)]`` in one call; all or nothing."""
+        keyed = [(self._who(w), normalize_rules(r)) for w, r in records]
+        self.db.store_many([(kind, value, self._numbers(r)) for (_, kind, value), r in keyed])
+        for (key, _, _), r in keyed:
+            self.records[key] = r
+
+    def delete_rules(self, who) -> None:
+        """delete_rules/1 (:152-164)."""
+        key, kind, value = self._who(who)
+        self.db.delete(kind, value)
+        self.records.pop(key, None)
+
+    def purge_rules(self) -> None:
+        """purge_rules/0 (:166-169)."""
+        self.db.purge()
+        self.records.clear()
+
+    def get_rules(self, who):
+        """get_rules/1 (:175-188): ``("ok", rules)`` or ``"not_found"``."""
+        key, _, _ = self._who(who)
+        return ("ok", list(self.records[key])) if key in self.records else "not_found"
+
+    def record_count(self) -> int:
+        """record_count/0 (:171-173)."""
+        return self.db.count()
+
+    def commit(self) -> None:
+        self.db.commit()
+
+    def _decide(self, clients: Sequence[dict], pubsubs: Sequence[str], topics: Sequence[bytes]):
+        """Per request ``None`` or ``(permission 0 | 1, source ACLDB_*, position of the deciding
+        rule in its record)``."""
+        table: Dict[tuple, int] = {}
+        ids: List[Optional[bytes]] = []
+        users: List[Optional[bytes]] = []
+        idx = []
+        for c in clients:
+            cid, usr = c.get("clientid"), c.get("username")
+            key = (None if cid is None else _bin(cid), None if usr is None else _bin(usr))
+            if key not in table:
+                table[key] = len(ids)
+                ids.append(key[0])
+                users.append(key[1])
+            idx.append(table[key])
+        act = [_ACTIONS[_atom(p)] for p in pubsubs]
+        if any(a == E.ACL_ALL for a in act):
+            raise ValueError("a request is publish or subscribe")
+        perm, src, pos = self.db.match([_bin(t) for t in topics], idx, act, ids, users)
+        return [None if int(p) == E.NONE else (int(p), int(s), int(q)) for p, s, q in zip(perm, src, pos)]
+
+    def authorize(self, clients: Sequence[dict], pubsubs: Sequence[str], topics: Sequence[bytes]):
+        """authorize/4 (:98-120) per request: ``("matched", "allow" | "deny")`` or ``"nomatch"``;
+        emqx_access_control's no_match default stays with the caller."""
+        return ["nomatch" if d is None else ("matched", "allow" if d[0] == E.ACL_ALLOW else "deny")
+                for d in self._decide(clients, pubsubs, topics)]

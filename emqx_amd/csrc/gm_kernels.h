@@ -307,6 +307,41 @@ struct AclArgs {
   unsigned long long* ctr = nullptr;  // optional: [4] ACL_CTR_*
 };
 hipError_t launch_acl(const AclArgs& a, hipStream_t s);
+// The built-in authorization database (gm_acldb.inc / gm_acldb.cpp), device pointers.  One launch
+// per pass of requests against the resident key tables, record pool and `all` stream.
+struct AclDbArgs {
+  const uint8_t* nb = nullptr;      // the pass's names
+  const uint32_t* no = nullptr;     // [n+1]
+  const uint32_t* client = nullptr; // [n] index into the client table
+  const uint32_t* action = nullptr; // [n] ACL_PUBLISH or ACL_SUBSCRIBE
+  uint32_t n = 0;
+  const uint8_t* cb = nullptr;      // client-id bytes
+  const uint32_t* co = nullptr;     // [n_clients+1]
+  const uint8_t* ub = nullptr;      // username bytes
+  const uint32_t* uo = nullptr;     // [n_clients+1]
+  const uint32_t* cf = nullptr;     // [n_clients] ACL_C_*_UNDEF
+  uint32_t n_clients = 0;
+  const void* tab[2] = {nullptr, nullptr};  // AdbSlot tables: client ids, usernames
+  uint64_t tmask[2] = {0, 0};       // slots - 1
+  const uint64_t* pool = nullptr;   // record pool (gm_acldb_match.h)
+  uint64_t pool_words = 0;
+  const uint64_t* all = nullptr;    // the `all` record: a tiled stream
+  uint32_t all_words = 0;
+  uint32_t all_fbase = 0, all_rules = 0;
+  const uint8_t* fb = nullptr;      // filter bytes
+  const uint32_t* fo = nullptr;     // [n_filters+1]
+  uint32_t n_filters = 0;
+  const uint8_t* kb = nullptr;      // key bytes
+  const uint32_t* ko = nullptr;     // [n_keys+1]
+  uint32_t n_keys = 0;
+  uint64_t test_mask = 0;
+  uint32_t* out_perm = nullptr;     // [n] ACL_DENY | ACL_ALLOW, NONE for nomatch
+  uint32_t* out_src = nullptr;      // [n] ADB_CLIENTID | ADB_USERNAME | ADB_ALL (NONE for nomatch)
+  uint32_t* out_pos = nullptr;      // [n] position of the deciding rule in its record
+  uint32_t* err = nullptr;          // set on a malformed run or slot, a bad client index or action
+  unsigned long long* ctr = nullptr;  // optional: [5] ADB_CTR_*
+};
+hipError_t launch_acldb(const AclDbArgs& a, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 8  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 9  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -231,6 +231,17 @@ SYMBOLS = {
                                    _P]),
     "emqxgm_acl_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "emqxgm_acl_stats": (C.c_int, [_P, _U64P]),
+    "emqxgm_acldb_create": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    "emqxgm_acldb_destroy": (None, [_P]),
+    "emqxgm_acldb_store": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32]),
+    "emqxgm_acldb_store_many": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "emqxgm_acldb_delete": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
+    "emqxgm_acldb_purge": (C.c_int, [_P]),
+    "emqxgm_acldb_commit": (C.c_int, [_P]),
+    "emqxgm_acldb_count": (C.c_int, [_P, _U64P]),
+    "emqxgm_acldb_match": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    "emqxgm_acldb_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emqxgm_acldb_stats": (C.c_int, [_P, _U64P]),
     "emqxgm_batcher_create": (C.c_int, [_P, C.POINTER(_BatcherCfg), C.POINTER(_P)]),
     "emqxgm_batcher_destroy": (None, [_P]),
     "emqxgm_batcher_add": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),
@@ -1140,3 +1151,118 @@ class Acl:
         a = (C.c_uint64 * 8)()
         self._check(self._lib.emqxgm_acl_stats(self._h, a), "acl_stats")
         return dict(zip(ACL_STAT_KEYS, (int(x) for x in a)))
+
+
+# include/emqx_gpumatch.h EMQXGM_ACLDB_*
+ACLDB_CLIENTID, ACLDB_USERNAME, ACLDB_ALL = 0, 1, 2
+ACLDB_MAX_RULES = 65536
+ACLDB_STAT_KEYS = ("clientid_records", "clientid_slots", "clientid_deleted", "username_records", "username_slots",
+                   "username_deleted", "max_chain", "all_rules", "live_words", "garbage_words", "rebuilds",
+                   "growths", "key_checked", "key_removed", "candidates", "removed", "deep", "all_tiles")
+
+
+class AclDb:
+    """The built-in authorization database resident on the device (emqxgm_acldb_*):
+    records keyed by client id, username or ``all``, ``emqx_authz_mnesia:authorize/4`` per request.
+    This is the C-ABI as it is, on numbers and bytes; ``emqx_amd.authz.BuiltinDb`` is the mirror of
+    the Erlang terms on top.  A rule is ``(perm, action, filter bytes)`` with the ACL_* numbers."""
+
+    def __init__(self, device: int = 0, word_hash_bits: int = 0):
+        self._lib = lib()
+        self._h = None
+        h = C.c_void_p()
+        rc = self._lib.emqxgm_acldb_create(device, word_hash_bits, C.byref(h))
+        if rc != 0:
+            raise EngineError(f"emqxgm_acldb_create failed: {rc}")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.emqxgm_acldb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int, what: str):
+        if rc < 0:
+            raise EngineError(f"{what} failed: {rc}")
+        return rc
+
+    def store(self, kind: int, key: bytes, rules: Sequence[Tuple[int, int, bytes]]) -> None:
+        """emqxgm_acldb_store: replaces the record of (kind, key); pending until commit."""
+        perm = np.asarray([r[0] for r in rules], np.uint32)
+        action = np.asarray([r[1] for r in rules], np.uint32)
+        fbuf, foff = pack([r[2] for r in rules], np.uint32)
+        kbuf = np.frombuffer(bytes(key), np.uint8)
+        self._check(self._lib.emqxgm_acldb_store(
+            self._h, kind, _ptr(kbuf), len(kbuf), _ptr(perm), _ptr(action), _ptr(fbuf),
+            foff.ctypes.data_as(C.c_void_p), len(rules)), "acldb_store")
+
+    def store_many(self, records: Sequence[Tuple[int, bytes, Sequence[Tuple[int, int, bytes]]]]) -> None:
+        """emqxgm_acldb_store_many: records are ``(kind, key, rules)``; all or nothing."""
+        records = list(records)
+        kind = np.asarray([r[0] for r in records], np.uint32)
+        kbuf, koff = pack([bytes(r[1]) for r in records], np.uint32)
+        roff = np.zeros(len(records) + 1, np.uint32)
+        np.cumsum([len(r[2]) for r in records], out=roff[1:])
+        flat = [x for r in records for x in r[2]]
+        perm = np.asarray([x[0] for x in flat], np.uint32)
+        action = np.asarray([x[1] for x in flat], np.uint32)
+        fbuf, foff = pack([x[2] for x in flat], np.uint32)
+        self._check(self._lib.emqxgm_acldb_store_many(
+            self._h, len(records), _ptr(kind), _ptr(kbuf), koff.ctypes.data_as(C.c_void_p),
+            roff.ctypes.data_as(C.c_void_p), _ptr(perm), _ptr(action), _ptr(fbuf),
+            foff.ctypes.data_as(C.c_void_p)), "acldb_store_many")
+
+    def delete(self, kind: int, key: bytes) -> None:
+        kbuf = np.frombuffer(bytes(key), np.uint8)
+        self._check(self._lib.emqxgm_acldb_delete(self._h, kind, _ptr(kbuf), len(kbuf)), "acldb_delete")
+
+    def purge(self) -> None:
+        self._check(self._lib.emqxgm_acldb_purge(self._h), "acldb_purge")
+
+    def commit(self) -> None:
+        self._check(self._lib.emqxgm_acldb_commit(self._h), "acldb_commit")
+
+    def count(self) -> int:
+        v = C.c_uint64()
+        self._check(self._lib.emqxgm_acldb_count(self._h, C.byref(v)), "acldb_count")
+        return int(v.value)
+
+    def match(self, names: Sequence[bytes], client: Sequence[int], action: Sequence[int],
+              clientids: Sequence[Optional[bytes]], usernames: Sequence[Optional[bytes]]):
+        """emqxgm_acldb_match: request i = (names[i], client[i], action[i]); the client table is
+        clientids / usernames (None: undefined).  -> (perm, src, pos), u32 [n] each, NONE for
+        nomatch."""
+        names = list(names)
+        n, nc = len(names), len(clientids)
+        assert len(usernames) == nc and len(client) == len(action) == n
+        buf, off = pack(names, np.uint32)
+        cbuf, coff = pack([c or b"" for c in clientids], np.uint32)
+        ubuf, uoff = pack([u or b"" for u in usernames], np.uint32)
+        cf = np.asarray([(ACL_NO_CLIENTID if c is None else 0) | (ACL_NO_USERNAME if u is None else 0)
+                         for c, u in zip(clientids, usernames)], np.uint32)
+        cl = np.asarray(client, np.uint32)
+        ac = np.asarray(action, np.uint32)
+        out = [np.full(n, NONE, np.uint32) for _ in range(3)]
+        self._check(self._lib.emqxgm_acldb_match(
+            self._h, _ptr(buf), off.ctypes.data_as(C.c_void_p), n, _ptr(cl), _ptr(ac), _ptr(cbuf),
+            coff.ctypes.data_as(C.c_void_p), _ptr(ubuf), uoff.ctypes.data_as(C.c_void_p), _ptr(cf), nc,
+            _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "acldb_match")
+        return tuple(out)
+
+    def tune(self, key: str, value: int) -> None:
+        self._check(self._lib.emqxgm_acldb_tune(self._h, key.encode(), int(value)), "acldb_tune")
+
+    def kernel_time_us(self) -> int:
+        """Kernel microseconds summed since tune("timing", 1)."""
+        return self._check(self._lib.emqxgm_acldb_tune(self._h, b"kernel_us", 0), "acldb_tune")
+
+    def stats(self) -> dict:
+        a = (C.c_uint64 * 20)()
+        self._check(self._lib.emqxgm_acldb_stats(self._h, a), "acldb_stats")
+        return dict(zip(ACLDB_STAT_KEYS, (int(x) for x in a)))

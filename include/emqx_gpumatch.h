@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 8
+#define EMQXGM_ABI_VERSION 9
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -613,6 +613,75 @@ int emqxgm_acl_tune(emqxgm_acl_t* a, const char* key, int64_t value);
  * candidates it removed, names deeper than 16 levels, records visited}; the last four since the
  * last set */
 int emqxgm_acl_stats(emqxgm_acl_t* a, uint64_t out[8]);
+
+/* ---- the built-in authorization database, resident on the device -------------
+ * emqx_authz_mnesia (apps/emqx_authz/src/emqx_authz_mnesia.erl): one record per principal, keyed
+ * {clientid, C}, {username, U} or all (:41-58), each an ordered list of
+ * {Permission, Action, TopicFilter}.  authorize/4 (:98-120) reads the record of the request's
+ * client id, the one of its username and the all record, and the first rule of
+ * clientid ++ username ++ all that matches decides (do_authorize/4, :222-229, each rule compiled
+ * as {Permission, all, Action, [TopicFilter]} by emqx_authz_rule:compile/1).  Keys are compared by
+ * byte equality over any bytes (the empty key included); the same bytes as a client id and as a
+ * username are two keys.  An undefined client id or username skips that read.  A filter that
+ * begins with "eq " is {eq, F} (compile_topic/1, emqx_authz_rule.erl:98-99); the placeholder feed
+ * and the topic match are those of the ACL lists above.  No answer rests on a hash.  A request
+ * costs its client's own rules plus the all rules, whatever the number of keys.  Limits: 65,536
+ * rules per record; the database as a whole has none below 2^32 pool words, filters and keys.
+ * Mutations (store, delete, purge) are pending until emqxgm_acldb_commit and invisible before. */
+#define EMQXGM_ACLDB_CLIENTID 0u /* key kind; also the source of an answer */
+#define EMQXGM_ACLDB_USERNAME 1u
+#define EMQXGM_ACLDB_ALL 2u
+typedef struct emqxgm_acldb emqxgm_acldb_t;
+int emqxgm_acldb_create(int32_t device, uint32_t word_hash_bits, emqxgm_acldb_t** out);
+void emqxgm_acldb_destroy(emqxgm_acldb_t* db);
+/* store_rules/2 (:132-150): replaces the record of (kind, key) by n_rules rules, rule k =
+ * {perm[k] (EMQXGM_ACL_DENY | ALLOW), action[k] (PUBLISH | SUBSCRIBE | ALL), filter
+ * filter_bytes[filter_offsets[k] .. filter_offsets[k+1])}.  The key is ignored for
+ * EMQXGM_ACLDB_ALL.  A record with no rules answers like an absent one and counts in
+ * emqxgm_acldb_count.  -EINVAL on a bad kind, permission, action or offsets or more than 65,536
+ * rules; nothing is then pending from the call. */
+int emqxgm_acldb_store(emqxgm_acldb_t* db, uint32_t kind, const uint8_t* key, uint32_t klen,
+                       const uint32_t* perm, const uint32_t* action, const uint8_t* filter_bytes,
+                       const uint32_t* filter_offsets, uint32_t n_rules);
+/* The same for n_records records at once, in order: record i has kind[i], the key
+ * key_bytes[key_offsets[i] .. key_offsets[i+1]) and the rules rule_offsets[i] ..
+ * rule_offsets[i+1] of perm / action / filter_offsets.  All or nothing. */
+int emqxgm_acldb_store_many(emqxgm_acldb_t* db, uint32_t n_records, const uint32_t* kind,
+                            const uint8_t* key_bytes, const uint32_t* key_offsets,
+                            const uint32_t* rule_offsets, const uint32_t* perm, const uint32_t* action,
+                            const uint8_t* filter_bytes, const uint32_t* filter_offsets);
+/* delete_rules/1 (:152-164); deleting an absent key is a no-op. */
+int emqxgm_acldb_delete(emqxgm_acldb_t* db, uint32_t kind, const uint8_t* key, uint32_t klen);
+/* purge_rules/0 (:166-169): drops every record and everything pending before the call. */
+int emqxgm_acldb_purge(emqxgm_acldb_t* db);
+/* Makes the pending mutations visible.  New and replaced runs are appended to the device pools
+ * and their table slots patched; a full rebuild (compaction and rehash) runs when a key table
+ * would pass the load "rebuild_load_pct" or the garbage words pass "rebuild_garbage_pct" percent
+ * of the live ones (the words of the all stream count like pool words).  After a commit that
+ * failed with -EIO the handle answers -EIO to every commit and match: destroy it. */
+int emqxgm_acldb_commit(emqxgm_acldb_t* db);
+/* record_count/0 (:171-173): committed records as they will be after the pending mutations. */
+int emqxgm_acldb_count(emqxgm_acldb_t* db, uint64_t* out);
+/* authorize/4 for a batch: requests and the client table as in emqxgm_acl_match (without
+ * who_bits).  Per request: out_perm = EMQXGM_ACL_DENY | ALLOW or EMQXGM_NONE for nomatch, out_src
+ * = EMQXGM_ACLDB_* of the deciding record, out_pos = the deciding rule's position in it (both
+ * EMQXGM_NONE for nomatch).  -EINVAL, before anything is launched, on a client index out of range
+ * or an action other than publish or subscribe; -EIO when a lane found a malformed run. */
+int emqxgm_acldb_match(emqxgm_acldb_t* db, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
+                       const uint32_t* client, const uint32_t* action, const uint8_t* clientid_bytes,
+                       const uint32_t* clientid_offsets, const uint8_t* username_bytes,
+                       const uint32_t* username_offsets, const uint32_t* client_flags,
+                       uint32_t n_clients, uint32_t* out_perm, uint32_t* out_src, uint32_t* out_pos);
+/* "pass_names", "counters", "timing" and the read-only "kernel_us" as emqxgm_acl_tune;
+ * "rebuild_load_pct" (1..50, default 50: a table's used slots, deleted ones included, in percent
+ * of its slots) and "rebuild_garbage_pct" (>= 1, default 100) */
+int emqxgm_acldb_tune(emqxgm_acldb_t* db, const char* key, int64_t value);
+/* out = {client-id records, slots, deleted slots, username records, slots, deleted slots, the
+ * longest probe chain of a stored key, rules of the all record, live words (pool and all
+ * stream), garbage words, full rebuilds, pool growths, key hits sent to the byte check, key hits it removed,
+ * filter candidates sent to the byte check, candidates it removed, names deeper than 16 levels,
+ * tiles of the all record, 0, 0}; the five counters since "counters" was last set */
+int emqxgm_acldb_stats(emqxgm_acldb_t* db, uint64_t out[20]);
 
 /* ---- single-driver batcher core: publish windows over the host pipes ---------------------
  * A caller that batches topics itself (one thread adding, flushing and collecting; bench.py's

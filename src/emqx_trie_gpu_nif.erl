@@ -49,7 +49,14 @@
     acl_open/2,
     acl_set/2,
     acl_match/2,
-    acl_close/1
+    acl_close/1,
+    acldb_open/2,
+    acldb_store/4,
+    acldb_delete/3,
+    acldb_purge/1,
+    acldb_commit/1,
+    acldb_match/2,
+    acldb_close/1
 ]).
 
 -on_load(init/0).
@@ -145,6 +152,26 @@ acl_set(_A, _Rules) -> ?NOT_LOADED.
 acl_match(_A, _ClientsAndRequests) -> ?NOT_LOADED.
 %% acl_close(A) -> ok
 acl_close(_A) -> ?NOT_LOADED.
+
+%% The built-in authorization database (emqx_authz_mnesia) resident on the device.
+%% acldb_open(Device, WordHashBits :: 0) -> {ok, D} | {error, Reason}
+acldb_open(_Device, _WordHashBits) -> ?NOT_LOADED.
+%% acldb_store(D, clientid | username | all, Key,
+%%             [{allow | deny, publish | subscribe | all, Topic}]) -> ok:
+%% store_rules/2; pending until acldb_commit/1
+acldb_store(_D, _Kind, _Key, _Rules) -> ?NOT_LOADED.
+%% acldb_delete(D, clientid | username | all, Key) -> ok: delete_rules/1
+acldb_delete(_D, _Kind, _Key) -> ?NOT_LOADED.
+%% acldb_purge(D) -> ok: purge_rules/0
+acldb_purge(_D) -> ?NOT_LOADED.
+%% acldb_commit(D) -> ok | {error, Reason}: makes the pending mutations visible
+acldb_commit(_D) -> ?NOT_LOADED.
+%% acldb_match(D, {[{ClientId | undefined, Username | undefined}],
+%%                 [{Name, ClientIndex, publish | subscribe}]}) ->
+%%     [{allow | deny, clientid | username | all, Position} | nomatch]: authorize/4 per request
+acldb_match(_D, _ClientsAndRequests) -> ?NOT_LOADED.
+%% acldb_close(D) -> ok
+acldb_close(_D) -> ?NOT_LOADED.
 %% snapshot_save(Res, Path :: binary()) -> ok | {error, Reason}: the committed index to a file
 snapshot_save(_Res, _Path) -> ?NOT_LOADED.
 %% snapshot_load(Res, Path :: binary()) -> ok | {error, Reason}: into a fresh resource, no build
