@@ -72,10 +72,11 @@ typedef struct {
   int publish;
 } gm_call;
 
-static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT, *ACL_RT, *ACLDB_RT;
+static ErlNifResourceType *RT, *CALL_RT, *RETAIN_RT, *RULESET_RT, *ACL_RT, *ACLDB_RT, *SHARE_RT;
 static ERL_NIF_TERM A_OK, A_ERROR, A_TRUE, A_FALSE, A_MOD, A_ROUTES, A_NONE, A_NODE, A_GROUP, A_SUB,
     A_SPIN_US, A_BG_BUILD, A_PUBLISH, A_UNDEFINED, A_REPORT_THREADS, A_EQ, A_WORDS, A_BINARY,
-    A_FAIL_THRESHOLD, A_EAGER, A_ALLOW, A_DENY, A_SUBSCRIBE, A_ALL, A_USERNAME, A_CLIENTID, A_SLOT, A_NOMATCH;
+    A_FAIL_THRESHOLD, A_EAGER, A_ALLOW, A_DENY, A_SUBSCRIBE, A_ALL, A_USERNAME, A_CLIENTID, A_SLOT, A_NOMATCH, A_DEFAULT, A_PICKED,
+    A_NO_SUBSCRIBERS, A_HOST_STRATEGY, A_STRATEGY[7]; /* A_STRATEGY: by EMQXGM_SHARE_* code */
 
 static int tab_init(term_tab* t, char* name) {
   t->lk = enif_rwlock_create(name);
@@ -2025,6 +2026,225 @@ static ERL_NIF_TERM nif_acldb_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM
   return A_OK;
 }
 
+/* ---- shared subscriptions: which member of a group gets a message --------------------------------
+ * emqx_shared_sub (emqx_shared_sub.erl): subscribe/3, unsubscribe/3 (:416-431) and cleanup_down/1
+ * (:509-519) are mirrored into an emqxgm_share_t, made visible by share_commit/1, and share_pick/2
+ * answers pick/6 (:309-379) for a batch of first dispatches.  Groups and subscribers are the
+ * caller's handles (alloc_handle/2); erlang:phash2/1 of the client id and of the topic and the
+ * random draw are computed by the caller, before the call.  do_route's share clause of
+ * emqx_trie_gpu stays on emqx_shared_sub:dispatch/3: one launch per publish would cost more than
+ * the ets:select it replaces; this entry is for callers that pick per window. */
+typedef struct {
+  emqxgm_share_t* s; /* NULL once closed */
+  ErlNifMutex* mu;
+} gm_share;
+
+static void gm_share_dtor(ErlNifEnv* env, void* obj) {
+  gm_share* g = (gm_share*)obj;
+  (void)env;
+  if (g->s) emqxgm_share_destroy(g->s);
+  if (g->mu) enif_mutex_destroy(g->mu);
+}
+
+static int get_share(ErlNifEnv* env, ERL_NIF_TERM t, gm_share** g) {
+  return enif_get_resource(env, t, SHARE_RT, (void**)g) && (*g)->mu;
+}
+
+static ERL_NIF_TERM share_rc(ErlNifEnv* env, int rc) {
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : A_OK;
+}
+
+/* share_open(Device, HashBits) -> {ok, S} | {error, Reason} (HashBits: 0 but in tests) */
+static ERL_NIF_TERM nif_share_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  int dev;
+  unsigned bits;
+  (void)argc;
+  if (!enif_get_int(env, argv[0], &dev) || !enif_get_uint(env, argv[1], &bits)) return enif_make_badarg(env);
+  gm_share* g = enif_alloc_resource(SHARE_RT, sizeof(gm_share));
+  memset(g, 0, sizeof *g);
+  g->mu = enif_mutex_create("emqx_trie_gpu.share");
+  const int rc = g->mu ? emqxgm_share_create(dev, bits, &g->s) : -ENOMEM;
+  if (rc) {
+    enif_release_resource(g);
+    return rc == -EINVAL ? enif_make_badarg(env) : err_term(env, rc);
+  }
+  ERL_NIF_TERM t = enif_make_resource(env, g);
+  enif_release_resource(g);
+  return enif_make_tuple2(env, A_OK, t);
+}
+
+/* share_subscribe(S, Group, Topic, Sub, Local :: boolean()) -> ok: subscribe/3, pending until
+ * share_commit/1.  Local: erlang:node(SubPid) =:= node(). */
+static ERL_NIF_TERM nif_share_subscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  unsigned group, sub;
+  ErlNifBinary t;
+  (void)argc;
+  if (!get_share(env, argv[0], &g) || !enif_get_uint(env, argv[1], &group) || !enif_inspect_binary(env, argv[2], &t) ||
+      t.size > GM_MAX_TOPIC || !enif_get_uint(env, argv[3], &sub) || (argv[4] != A_TRUE && argv[4] != A_FALSE))
+    return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->s ? emqxgm_share_subscribe(g->s, group, t.data, (uint32_t)t.size, sub, argv[4] == A_TRUE) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  return share_rc(env, rc);
+}
+
+/* share_unsubscribe(S, Group, Topic, Sub) -> ok: unsubscribe/3, pending until the commit */
+static ERL_NIF_TERM nif_share_unsubscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  unsigned group, sub;
+  ErlNifBinary t;
+  (void)argc;
+  if (!get_share(env, argv[0], &g) || !enif_get_uint(env, argv[1], &group) || !enif_inspect_binary(env, argv[2], &t) ||
+      t.size > GM_MAX_TOPIC || !enif_get_uint(env, argv[3], &sub))
+    return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->s ? emqxgm_share_unsubscribe(g->s, group, t.data, (uint32_t)t.size, sub) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  return share_rc(env, rc);
+}
+
+/* share_down(S, Sub) -> ok: cleanup_down/1, pending until the commit */
+static ERL_NIF_TERM nif_share_down(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  unsigned sub;
+  (void)argc;
+  if (!get_share(env, argv[0], &g) || !enif_get_uint(env, argv[1], &sub)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->s ? emqxgm_share_subscriber_down(g->s, sub) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  return share_rc(env, rc);
+}
+
+/* share_strategy(S, Group | default, Strategy) -> ok: the group's strategy (strategy/1), or the
+ * default for groups that have none set; pending until the commit */
+static ERL_NIF_TERM nif_share_strategy(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  unsigned group = EMQXGM_NONE;
+  uint32_t code = 0;
+  (void)argc;
+  if (!get_share(env, argv[0], &g) || (argv[1] != A_DEFAULT && !enif_get_uint(env, argv[1], &group)))
+    return enif_make_badarg(env);
+  while (code < 7 && argv[2] != A_STRATEGY[code]) ++code;
+  if (code == 7 || (argv[1] != A_DEFAULT && group == EMQXGM_NONE)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->s ? emqxgm_share_set_strategy(g->s, group, code) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  return share_rc(env, rc);
+}
+
+/* share_commit(S) -> ok | {error, Reason}: makes the pending mutations visible */
+static ERL_NIF_TERM nif_share_commit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  (void)argc;
+  if (!get_share(env, argv[0], &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  const int rc = g->s ? emqxgm_share_commit(g->s) : -EINVAL;
+  enif_mutex_unlock(g->mu);
+  return share_rc(env, rc);
+}
+
+/* share_pick(S, [{Topic, Group, Hc, Ht, Draw, State | undefined}]) ->
+ *     [{picked | no_subscribers | host_strategy, Sub | undefined, State | undefined, Count}]
+ *     | {error, Reason}: pick/6 per request.  Hc = erlang:phash2(ClientId), Ht =
+ * erlang:phash2(SourceTopic), Draw = 32 random bits, State = the publisher's
+ * {shared_sub_round_robin, Group, Topic} entry; the State returned is to be stored back. */
+static ERL_NIF_TERM nif_share_pick(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  packed p;
+  (void)argc;
+  if (!get_share(env, argv[0], &g)) return enif_make_badarg(env);
+  int rc = pack_list(env, argv[1], 1, &p);
+  const size_t rn = p.n ? p.n : 1;
+  uint32_t* o = rc ? NULL : off32(&p);
+  uint32_t* rq = rc ? NULL : enif_alloc(sizeof(uint32_t) * rn * 9); /* group, hc, ht, draw, state, out[4] */
+  if (!rc && (!o || !rq)) rc = -ENOMEM;
+  if (!rc && p.off[p.n] > 0xFFFFFFFFull) rc = -E2BIG;
+  ERL_NIF_TERM head, l = argv[1];
+  for (unsigned i = 0; !rc && i < p.n; ++i) {
+    int ar;
+    const ERL_NIF_TERM* el;
+    unsigned v[5] = {0, 0, 0, 0, EMQXGM_NONE};
+    enif_get_list_cell(env, l, &head, &l);
+    enif_get_tuple(env, head, &ar, &el);
+    if (ar != 6) rc = -EINVAL;
+    for (int k = 0; !rc && k < 5; ++k)
+      if (!(k == 4 && el[5] == A_UNDEFINED) && (!enif_get_uint(env, el[k + 1], &v[k]) || (k == 4 && v[k] == EMQXGM_NONE)))
+        rc = -EINVAL;
+    for (int k = 0; !rc && k < 5; ++k) rq[k * rn + i] = v[k];
+  }
+  ERL_NIF_TERM res = 0;
+  if (!rc) {
+    uint32_t* out = rq + 5 * rn;
+    enif_mutex_lock(g->mu);
+    rc = g->s ? emqxgm_share_pick(g->s, p.n, rq, p.bytes, o, rq + rn, rq + 2 * rn, rq + 3 * rn, rq + 4 * rn, out) : -EINVAL;
+    enif_mutex_unlock(g->mu);
+    if (!rc) {
+      res = enif_make_list(env, 0);
+      for (uint32_t i = p.n; i-- > 0;) {
+        const uint32_t* r = out + 4 * (size_t)i;
+        const ERL_NIF_TERM st = r[1] == EMQXGM_SHARE_PICKED           ? A_PICKED
+                                : r[1] == EMQXGM_SHARE_NO_SUBSCRIBERS ? A_NO_SUBSCRIBERS
+                                                                      : A_HOST_STRATEGY;
+        res = enif_make_list_cell(env,
+                                  enif_make_tuple4(env, st, r[0] == EMQXGM_NONE ? A_UNDEFINED : enif_make_uint(env, r[0]),
+                                                   r[2] == EMQXGM_NONE ? A_UNDEFINED : enif_make_uint(env, r[2]),
+                                                   enif_make_uint(env, r[3])),
+                                  res);
+      }
+    }
+  }
+  enif_free(o);
+  enif_free(rq);
+  packed_free(&p);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* share_members(S, Group, Topic) -> [{Sub, Local :: boolean()}] | {error, Reason}: subscribers/2,
+ * the committed members in subscribe order, from the host mirror (no device call) */
+static ERL_NIF_TERM nif_share_members(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  unsigned group;
+  ErlNifBinary t;
+  (void)argc;
+  if (!get_share(env, argv[0], &g) || !enif_get_uint(env, argv[1], &group) || !enif_inspect_binary(env, argv[2], &t) ||
+      t.size > GM_MAX_TOPIC)
+    return enif_make_badarg(env);
+  uint32_t n = 0, n2 = 0;
+  uint32_t* m = NULL;
+  enif_mutex_lock(g->mu);
+  int rc = g->s ? emqxgm_share_members(g->s, group, t.data, (uint32_t)t.size, NULL, 0, &n) : -EINVAL;
+  if (!rc && n) {
+    m = enif_alloc(sizeof(uint32_t) * n);
+    rc = m ? emqxgm_share_members(g->s, group, t.data, (uint32_t)t.size, m, n, &n2) : -ENOMEM;
+  }
+  enif_mutex_unlock(g->mu);
+  ERL_NIF_TERM res = enif_make_list(env, 0);
+  if (!rc)
+    for (uint32_t i = n2 < n ? n2 : n; i-- > 0;)
+      res = enif_make_list_cell(env,
+                                enif_make_tuple2(env, enif_make_uint(env, m[i] & ~EMQXGM_SHARE_LOCAL_MEMBER),
+                                                 (m[i] & EMQXGM_SHARE_LOCAL_MEMBER) ? A_TRUE : A_FALSE),
+                                res);
+  enif_free(m);
+  if (rc == -EINVAL) return enif_make_badarg(env);
+  return rc ? err_term(env, rc) : res;
+}
+
+/* share_close(S) -> ok: frees the device table now (the resource's destructor otherwise) */
+static ERL_NIF_TERM nif_share_close(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_share* g;
+  (void)argc;
+  if (!get_share(env, argv[0], &g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->mu);
+  if (g->s) emqxgm_share_destroy(g->s);
+  g->s = NULL;
+  enif_mutex_unlock(g->mu);
+  return A_OK;
+}
+
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
@@ -2034,7 +2254,8 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   RULESET_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_ruleset", gm_ruleset_dtor, ERL_NIF_RT_CREATE, NULL);
   ACL_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_acl", gm_acl_dtor, ERL_NIF_RT_CREATE, NULL);
   ACLDB_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_acldb", gm_acldb_dtor, ERL_NIF_RT_CREATE, NULL);
-  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || !ACL_RT || !ACLDB_RT ||
+  SHARE_RT = enif_open_resource_type(env, NULL, "emqx_trie_gpu_share", gm_share_dtor, ERL_NIF_RT_CREATE, NULL);
+  if (!RT || !CALL_RT || !RETAIN_RT || !RULESET_RT || !ACL_RT || !ACLDB_RT || !SHARE_RT ||
       emqxgm_abi_version() != EMQXGM_ABI_VERSION)
     return -1;
   A_OK = enif_make_atom(env, "ok");
@@ -2065,6 +2286,17 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   A_CLIENTID = enif_make_atom(env, "clientid");
   A_NOMATCH = enif_make_atom(env, "nomatch");
   A_SLOT = enif_make_atom(env, "slot");
+  A_DEFAULT = enif_make_atom(env, "default");
+  A_PICKED = enif_make_atom(env, "picked");
+  A_NO_SUBSCRIBERS = enif_make_atom(env, "no_subscribers");
+  A_HOST_STRATEGY = enif_make_atom(env, "host_strategy");
+  A_STRATEGY[EMQXGM_SHARE_RANDOM] = enif_make_atom(env, "random");
+  A_STRATEGY[EMQXGM_SHARE_ROUND_ROBIN] = enif_make_atom(env, "round_robin");
+  A_STRATEGY[EMQXGM_SHARE_ROUND_ROBIN_PER_GROUP] = enif_make_atom(env, "round_robin_per_group");
+  A_STRATEGY[EMQXGM_SHARE_STICKY] = enif_make_atom(env, "sticky");
+  A_STRATEGY[EMQXGM_SHARE_LOCAL] = enif_make_atom(env, "local");
+  A_STRATEGY[EMQXGM_SHARE_HASH_CLIENTID] = enif_make_atom(env, "hash_clientid");
+  A_STRATEGY[EMQXGM_SHARE_HASH_TOPIC] = enif_make_atom(env, "hash_topic");
   return 0;
 }
 
@@ -2122,6 +2354,15 @@ static ErlNifFunc funcs[] = {
     {"acldb_commit", 1, nif_acldb_commit, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acldb_match", 2, nif_acldb_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acldb_close", 1, nif_acldb_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"share_open", 2, nif_share_open, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"share_subscribe", 5, nif_share_subscribe, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_unsubscribe", 4, nif_share_unsubscribe, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_down", 2, nif_share_down, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_strategy", 3, nif_share_strategy, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_commit", 1, nif_share_commit, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"share_pick", 2, nif_share_pick, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"share_members", 3, nif_share_members, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_close", 1, nif_share_close, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(emqx_trie_gpu_nif, funcs, load, NULL, NULL, NULL)

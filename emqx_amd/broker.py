@@ -8,6 +8,9 @@
 * ``publish(Topic)`` / ``publish_batch([Topic])`` -- route(aggre(match_routes(Topic))) of
   emqx_broker:publish/1 (:218-300): per topic the aggre/1 entries ``(To, Node | Group)`` and the
   local dispatches ``(To, Sub)`` of the entries ``{To, node()}`` (dispatch/2, :326-355).
+* ``publish_shared_batch([Topic], [Message])`` -- the ``{To, Group}`` entries of the same answer
+  handed to ``emqx_shared_sub:dispatch/3`` (:270-275): the member each one goes to, picked on the
+  device from ``Broker.shared`` (``emqx_amd.shared_sub.SharedSubs``).
 
 The match, aggre and the per-subscriber expansion all run on the device
 (``emqxgm_publish_batch``); this class only maps node / group / subscriber names to the
@@ -43,6 +46,15 @@ class Broker:
         self._local: Dict[bytes, set] = {}
         self.engine.set_local_node(self._nodes.id(node))
         self._dirty = True
+        self._shared = None
+
+    @property
+    def shared(self):
+        """emqx_shared_sub of this node (created on first use; group names are the broker's)."""
+        if self._shared is None:
+            from .shared_sub import SharedSubs
+            self._shared = SharedSubs(node=self.node, device=self.engine.device, groups=self._groups)
+        return self._shared
 
     # ---- routes to other nodes / shared groups ----
     def _dest(self, dest) -> Tuple[int, int]:
@@ -111,3 +123,26 @@ class Broker:
 
     def publish(self, topic: bytes):
         return self.publish_batch([topic])[0]
+
+    def publish_shared_batch(self, topics: Sequence[bytes], messages: Sequence[Tuple]):
+        """Per topic the ``{To, Group}`` entries of ``publish_batch`` with the member
+        ``emqx_shared_sub:dispatch/3`` sends to: [(To, Group, (status, member, state out, Count))],
+        as ``SharedSubs.dispatch_batch`` answers.  messages[i] = (hc, ht, draw, states) of topic i:
+        ``erlang:phash2`` of its client id and of its topic, 32 random bits, and the publisher's
+        ``round_robin`` states ``{(Group, To): state}`` (or None)."""
+        assert len(messages) == len(topics)
+        self.commit()
+        res = self.engine.publish(list(topics))
+        fb = self.engine.filter_bytes
+        reqs, owner = [], []
+        for i in range(len(topics)):
+            hc, ht, draw, states = messages[i]
+            for f, d in res.routes(i):
+                if d & DEST_GROUP:
+                    to, group = fb(f), self._groups.names[d & ~DEST_GROUP]
+                    reqs.append((group, to, hc, ht, draw, (states or {}).get((group, to))))
+                    owner.append(i)
+        out = [[] for _ in topics]
+        for i, r, a in zip(owner, reqs, self.shared.dispatch_batch(reqs) if reqs else []):
+            out[i].append((r[1], r[0], a))
+        return out

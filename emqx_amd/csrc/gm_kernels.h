@@ -342,6 +342,31 @@ struct AclDbArgs {
   unsigned long long* ctr = nullptr;  // optional: [5] ADB_CTR_*
 };
 hipError_t launch_acldb(const AclDbArgs& a, hipStream_t s);
+// Shared subscriptions (gm_share.inc / gm_share.cpp), device pointers.  One launch per pass of
+// requests against the resident key table and member pool (gm_share_match.h).
+struct ShareArgs {
+  const uint32_t* group = nullptr;  // [n] the request's group
+  const uint8_t* rb = nullptr;      // the pass's topics
+  const uint32_t* ro = nullptr;     // [n+1]
+  const uint32_t* hc = nullptr;     // [n] erlang:phash2(ClientId)
+  const uint32_t* ht = nullptr;     // [n] erlang:phash2(SourceTopic)
+  const uint32_t* draw = nullptr;   // [n] 32 random bits
+  const uint32_t* state = nullptr;  // [n] round_robin state in, NONE for undefined
+  uint32_t n = 0;
+  const void* tab = nullptr;        // ShSlot table
+  uint64_t tmask = 0;               // slots - 1
+  const uint32_t* pool = nullptr;   // member pool
+  uint64_t pool_words = 0;
+  const uint8_t* kb = nullptr;      // key bytes
+  const uint32_t* ko = nullptr;     // [n_keys+1]
+  const uint32_t* kg = nullptr;     // [n_keys] group of the key
+  uint32_t n_keys = 0;
+  uint64_t tag_mask = 0;
+  uint4* out = nullptr;             // [n] {member | NONE, SH_* status, state out, Count | key index}
+  uint32_t* err = nullptr;          // set on a key index, run or member position out of bounds
+  bool stage = false;               // the block's topics through LDS before hashing
+};
+hipError_t launch_share(const ShareArgs& a, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

@@ -17,6 +17,7 @@
 #include "gm_ruleset_match.h"
 #include "gm_acl_match.h"
 #include "gm_acldb_match.h"
+#include "gm_share_match.h"
 
 namespace gm {
 
@@ -203,6 +204,7 @@ __device__ __forceinline__ uint3 stg_load(const uint3* stg, const StgFmt& F, uin
 #include "gm_ruleset.inc"
 #include "gm_acl.inc"
 #include "gm_acldb.inc"
+#include "gm_share.inc"
 
 __global__ __launch_bounds__(WG) void k_row64(const uint32_t* row, uint64_t base, uint64_t* out,
                                               uint32_t m) {
@@ -1215,6 +1217,14 @@ hipError_t launch_acldb(const AclDbArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
   hipLaunchKernelGGL(k_acldb, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_share(const ShareArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
+  if (a.stage) hipLaunchKernelGGL(k_share<true>, grid, dim3(WG), 0, s, a);
+  else hipLaunchKernelGGL(k_share<false>, grid, dim3(WG), 0, s, a);
   return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 9  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 10  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -242,6 +242,18 @@ SYMBOLS = {
     "emqxgm_acldb_match": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "emqxgm_acldb_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "emqxgm_acldb_stats": (C.c_int, [_P, _U64P]),
+    "emqxgm_share_create": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    "emqxgm_share_destroy": (None, [_P]),
+    "emqxgm_share_subscribe": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "emqxgm_share_unsubscribe": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.c_uint32]),
+    "emqxgm_share_subscriber_down": (C.c_int, [_P, C.c_uint32]),
+    "emqxgm_share_set_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    "emqxgm_share_commit": (C.c_int, [_P]),
+    "emqxgm_share_pick": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "emqxgm_share_members": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _U32P]),
+    "emqxgm_share_counter": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _U32P]),
+    "emqxgm_share_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emqxgm_share_stats": (C.c_int, [_P, _U64P]),
     "emqxgm_batcher_create": (C.c_int, [_P, C.POINTER(_BatcherCfg), C.POINTER(_P)]),
     "emqxgm_batcher_destroy": (None, [_P]),
     "emqxgm_batcher_add": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),
@@ -1266,3 +1278,107 @@ class AclDb:
         a = (C.c_uint64 * 20)()
         self._check(self._lib.emqxgm_acldb_stats(self._h, a), "acldb_stats")
         return dict(zip(ACLDB_STAT_KEYS, (int(x) for x in a)))
+
+
+# include/emqx_gpumatch.h EMQXGM_SHARE_*
+SHARE_STRATEGIES = ("random", "round_robin", "round_robin_per_group", "sticky", "local", "hash_clientid",
+                    "hash_topic")
+SHARE_PICKED, SHARE_NO_SUBSCRIBERS, SHARE_HOST_STRATEGY = 0, 1, 2
+SHARE_LOCAL_MEMBER = 0x80000000
+SHARE_STAT_KEYS = ("keys", "slots", "deleted", "max_chain", "members", "live_words", "garbage_words",
+                   "load_rebuilds", "garbage_rebuilds", "growths", "counters", "pending")
+
+
+class SharedSub:
+    """Shared-subscription membership resident on the device (emqxgm_share_*):
+    ``emqx_shared_sub:pick/6`` per request.  This is the C-ABI as it is, on handles and bytes;
+    ``emqx_amd.shared_sub.SharedSubs`` is the mirror with the reference's names on top."""
+
+    def __init__(self, device: int = 0, hash_bits: int = 0):
+        self._lib = lib()
+        self._h = None
+        h = C.c_void_p()
+        rc = self._lib.emqxgm_share_create(device, hash_bits, C.byref(h))
+        if rc != 0:
+            raise EngineError(f"emqxgm_share_create failed: {rc}")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.emqxgm_share_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int, what: str):
+        if rc < 0:
+            raise EngineError(f"{what} failed: {rc}")
+        return rc
+
+    def subscribe(self, group: int, topic: bytes, sub: int, local: bool = True) -> None:
+        t = np.frombuffer(bytes(topic), np.uint8)
+        self._check(self._lib.emqxgm_share_subscribe(self._h, group, _ptr(t), len(t), sub, int(local)),
+                    "share_subscribe")
+
+    def unsubscribe(self, group: int, topic: bytes, sub: int) -> None:
+        t = np.frombuffer(bytes(topic), np.uint8)
+        self._check(self._lib.emqxgm_share_unsubscribe(self._h, group, _ptr(t), len(t), sub), "share_unsubscribe")
+
+    def subscriber_down(self, sub: int) -> None:
+        self._check(self._lib.emqxgm_share_subscriber_down(self._h, sub), "share_subscriber_down")
+
+    def set_strategy(self, group: Optional[int], strategy) -> None:
+        """strategy: a code or one of SHARE_STRATEGIES; group None: the default."""
+        code = SHARE_STRATEGIES.index(strategy) if isinstance(strategy, str) else int(strategy)
+        self._check(self._lib.emqxgm_share_set_strategy(self._h, NONE if group is None else group, code),
+                    "share_set_strategy")
+
+    def commit(self) -> None:
+        self._check(self._lib.emqxgm_share_commit(self._h), "share_commit")
+
+    def pick(self, groups, topics: Sequence[bytes], hc, ht, draw, state) -> np.ndarray:
+        """emqxgm_share_pick -> u32 [n, 4]: member | NONE, status, round_robin state out, Count.
+        state: NONE for undefined."""
+        topics = list(topics)
+        n = len(topics)
+        buf, off = pack(topics, np.uint32)
+        arrs = [np.ascontiguousarray(np.asarray(a, np.uint64).astype(np.uint32)) for a in (groups, hc, ht, draw, state)]
+        assert all(len(a) == n for a in arrs)
+        out = np.full((n, 4), NONE, np.uint32)
+        self._check(self._lib.emqxgm_share_pick(
+            self._h, n, _ptr(arrs[0]), _ptr(buf), off.ctypes.data_as(C.c_void_p), _ptr(arrs[1]), _ptr(arrs[2]),
+            _ptr(arrs[3]), _ptr(arrs[4]), _ptr(out)), "share_pick")
+        return out
+
+    def members(self, group: int, topic: bytes):
+        """emqxgm_share_members -> [(handle, local)] in subscribe order."""
+        t = np.frombuffer(bytes(topic), np.uint8)
+        n = C.c_uint32()
+        self._check(self._lib.emqxgm_share_members(self._h, group, _ptr(t), len(t), None, 0, C.byref(n)),
+                    "share_members")
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self._check(self._lib.emqxgm_share_members(self._h, group, _ptr(t), len(t), _ptr(out), len(out),
+                                                   C.byref(n)), "share_members")
+        return [(int(m) & ~SHARE_LOCAL_MEMBER, bool(int(m) & SHARE_LOCAL_MEMBER)) for m in out[:n.value]]
+
+    def counter(self, group: int, topic: bytes) -> Optional[int]:
+        t = np.frombuffer(bytes(topic), np.uint8)
+        v = C.c_uint32()
+        self._check(self._lib.emqxgm_share_counter(self._h, group, _ptr(t), len(t), C.byref(v)), "share_counter")
+        return None if v.value == NONE else int(v.value)
+
+    def tune(self, key: str, value: int) -> None:
+        self._check(self._lib.emqxgm_share_tune(self._h, key.encode(), int(value)), "share_tune")
+
+    def kernel_time_us(self) -> int:
+        """Kernel microseconds summed since tune("timing", 1)."""
+        return self._check(self._lib.emqxgm_share_tune(self._h, b"kernel_us", 0), "share_tune")
+
+    def stats(self) -> dict:
+        a = (C.c_uint64 * 12)()
+        self._check(self._lib.emqxgm_share_stats(self._h, a), "share_stats")
+        return dict(zip(SHARE_STAT_KEYS, (int(x) for x in a)))

@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 9
+#define EMQXGM_ABI_VERSION 10
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -682,6 +682,87 @@ int emqxgm_acldb_tune(emqxgm_acldb_t* db, const char* key, int64_t value);
  * filter candidates sent to the byte check, candidates it removed, names deeper than 16 levels,
  * tiles of the all record, 0, 0}; the five counters since "counters" was last set */
 int emqxgm_acldb_stats(emqxgm_acldb_t* db, uint64_t out[20]);
+
+/* ---- shared subscriptions: which member of a group gets a message -------------
+ * emqx_shared_sub (apps/emqx/src/emqx_shared_sub.erl): a bag of {Group, Topic, SubPid} (:104-117);
+ * subscribers/2 (:391-392) gives a key's members in subscribe order and pick/6 (:309-379) applies
+ * the group's strategy (strategy/1, :159-164).  This handle answers the first dispatch
+ * (dispatch/3, FailedSubs = #{}) of a batch of {To, Group} entries of emqx_broker:publish/1
+ * (emqx_broker.erl:270-275, EMQXGM_DEST_GROUP | group in emqxgm_publish_batch's answers).  Groups
+ * and members are handles below 2^31 that the caller assigns.  Keys (group, topic) are compared by
+ * byte equality over any bytes: the empty topic, "+", "#" and "a/#" are keys like any other.  No
+ * answer rests on a hash.  Redispatch after a nack (dispatch/4 with FailedSubs) and the ack
+ * protocol stay with the caller.  Mutations (subscribe, unsubscribe, subscriber_down,
+ * set_strategy) are pending, in call order, until emqxgm_share_commit and invisible before. */
+#define EMQXGM_SHARE_RANDOM 0u /* strategy/0 (:78-85) */
+#define EMQXGM_SHARE_ROUND_ROBIN 1u /* the default of a new handle, as emqx_schema's */
+#define EMQXGM_SHARE_ROUND_ROBIN_PER_GROUP 2u
+#define EMQXGM_SHARE_STICKY 3u
+#define EMQXGM_SHARE_LOCAL 4u
+#define EMQXGM_SHARE_HASH_CLIENTID 5u
+#define EMQXGM_SHARE_HASH_TOPIC 6u
+#define EMQXGM_SHARE_PICKED 0u /* status of an answer */
+#define EMQXGM_SHARE_NO_SUBSCRIBERS 1u
+#define EMQXGM_SHARE_HOST_STRATEGY 2u /* sticky: the caller decides, from emqxgm_share_members */
+#define EMQXGM_SHARE_LOCAL_MEMBER 0x80000000u /* emqxgm_share_members: bit of a local member */
+typedef struct emqxgm_share emqxgm_share_t;
+/* hash_bits 0 is production; 1..16 keeps that many bits of a key's tag (collision tests). */
+int emqxgm_share_create(int32_t device, uint32_t hash_bits, emqxgm_share_t** out);
+void emqxgm_share_destroy(emqxgm_share_t* s);
+/* subscribe/3 (:416-425): appends sub to the members of (group, topic); a triple already present
+ * keeps its position.  Either way a group whose strategy is round_robin_per_group at that moment
+ * has the key's counter set to 0 (maybe_insert_round_robin_count/1, :484-487).  local: whether
+ * the member is on this node (erlang:node(Pid) =:= node(), :349).  -EINVAL on a handle >= 2^31 or
+ * a triple subscribed (committed or pending) with the other local flag. */
+int emqxgm_share_subscribe(emqxgm_share_t* s, uint32_t group, const uint8_t* topic, uint32_t len,
+                           uint32_t sub, uint32_t local);
+/* unsubscribe/3 (:426-431): removes the triple; a later subscribe appends at the end.  A key whose
+ * last member leaves is absent, and its counter is deleted if the group's strategy is
+ * round_robin_per_group at that moment (maybe_delete_round_robin_count/1, :489-494). */
+int emqxgm_share_unsubscribe(emqxgm_share_t* s, uint32_t group, const uint8_t* topic, uint32_t len,
+                             uint32_t sub);
+/* cleanup_down/1 (:509-519): removes sub from every key. */
+int emqxgm_share_subscriber_down(emqxgm_share_t* s, uint32_t sub);
+/* strategy/1 (:159-164): the strategy of a group, or with group = EMQXGM_NONE the default for
+ * groups that have none set.  -EINVAL on a strategy code out of range. */
+int emqxgm_share_set_strategy(emqxgm_share_t* s, uint32_t group, uint32_t strategy);
+/* Makes the pending mutations visible.  Rewritten member runs and new keys are appended to the
+ * device pools and their table slots patched; a full rebuild (compaction and rehash) runs when the
+ * key table would pass the load "rebuild_load_pct" or the garbage words pass "rebuild_garbage_pct"
+ * percent of the live ones.  After a commit that failed with -EIO the handle answers -EIO to every
+ * later call: destroy it. */
+int emqxgm_share_commit(emqxgm_share_t* s);
+/* pick/6 for n requests: request i is on the key (groups[i], key_bytes[key_offsets[i] ..
+ * key_offsets[i+1])) with hc[i] = erlang:phash2(ClientId), ht[i] = erlang:phash2(SourceTopic),
+ * draw[i] = 32 random bits (the member is 1 + draw rem Count where the reference calls
+ * rand:uniform(Count)) and state[i] = the publisher's round_robin state for the key
+ * (erlang:get({shared_sub_round_robin, Group, Topic}), :367) or EMQXGM_NONE for undefined.
+ * out[4i..4i+3] = {member handle or EMQXGM_NONE, EMQXGM_SHARE_* status, round_robin state to
+ * store (state[i] unchanged unless round_robin ran over two or more members), Count = the key's
+ * members}.  A key of one member answers that member before any strategy (:346-347).
+ * round_robin_per_group requests of one call on one key take consecutive counter values in
+ * request order (:373-379).  -EINVAL, before anything is launched, on non-monotone offsets or a
+ * group >= 2^31; -EIO when a lane found a malformed table or run. */
+int emqxgm_share_pick(emqxgm_share_t* s, uint32_t n, const uint32_t* groups, const uint8_t* key_bytes,
+                      const uint32_t* key_offsets, const uint32_t* hc, const uint32_t* ht,
+                      const uint32_t* draw, const uint32_t* state, uint32_t* out);
+/* subscribers/2 (:391-392): *n_out = the committed members of (group, topic), the first
+ * min(cap, *n_out) into out in order, EMQXGM_SHARE_LOCAL_MEMBER set on the local ones.  From the
+ * host mirror: no device call. */
+int emqxgm_share_members(emqxgm_share_t* s, uint32_t group, const uint8_t* topic, uint32_t len,
+                         uint32_t* out, uint32_t cap, uint32_t* n_out);
+/* The key's round_robin_per_group counter, EMQXGM_NONE when it has none (for tests). */
+int emqxgm_share_counter(emqxgm_share_t* s, uint32_t group, const uint8_t* topic, uint32_t len,
+                         uint32_t* out);
+/* "pass_names" (requests per launch), "timing" and the read-only "kernel_us" as emqxgm_acl_tune;
+ * "rebuild_load_pct" (1..50, default 50) and "rebuild_garbage_pct" (>= 1, default 100);
+ * "stage_lds" (default 1: a block's topics go through LDS before they are hashed; 0 hashes them
+ * from global memory, the slower side of the A/B in MEASUREMENTS.md r16) */
+int emqxgm_share_tune(emqxgm_share_t* s, const char* key, int64_t value);
+/* out = {keys, table slots, deleted slots, the longest probe chain of a stored key, members, live
+ * pool words, garbage words, rebuilds forced by the table's load, rebuilds forced by garbage, pool
+ * growths, counters held, pending mutations} */
+int emqxgm_share_stats(emqxgm_share_t* s, uint64_t out[12]);
 
 /* ---- single-driver batcher core: publish windows over the host pipes ---------------------
  * A caller that batches topics itself (one thread adding, flushing and collecting; bench.py's

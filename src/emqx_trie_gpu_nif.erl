@@ -56,7 +56,16 @@
     acldb_purge/1,
     acldb_commit/1,
     acldb_match/2,
-    acldb_close/1
+    acldb_close/1,
+    share_open/2,
+    share_subscribe/5,
+    share_unsubscribe/4,
+    share_down/2,
+    share_strategy/3,
+    share_commit/1,
+    share_pick/2,
+    share_members/3,
+    share_close/1
 ]).
 
 -on_load(init/0).
@@ -172,6 +181,33 @@ acldb_commit(_D) -> ?NOT_LOADED.
 acldb_match(_D, _ClientsAndRequests) -> ?NOT_LOADED.
 %% acldb_close(D) -> ok
 acldb_close(_D) -> ?NOT_LOADED.
+
+%% Shared subscriptions (emqx_shared_sub): the membership resident on the device, pick/6 per
+%% request.  Groups and subscribers are handles (alloc_handle/2).
+%% share_open(Device, HashBits :: 0) -> {ok, S} | {error, Reason}
+share_open(_Device, _HashBits) -> ?NOT_LOADED.
+%% share_subscribe(S, Group, Topic, Sub, Local :: boolean()) -> ok: subscribe/3; pending until
+%% share_commit/1.  Local = (erlang:node(SubPid) =:= node()).
+share_subscribe(_S, _Group, _Topic, _Sub, _Local) -> ?NOT_LOADED.
+%% share_unsubscribe(S, Group, Topic, Sub) -> ok: unsubscribe/3
+share_unsubscribe(_S, _Group, _Topic, _Sub) -> ?NOT_LOADED.
+%% share_down(S, Sub) -> ok: cleanup_down/1
+share_down(_S, _Sub) -> ?NOT_LOADED.
+%% share_strategy(S, Group | default, Strategy :: emqx_shared_sub:strategy()) -> ok
+share_strategy(_S, _Group, _Strategy) -> ?NOT_LOADED.
+%% share_commit(S) -> ok | {error, Reason}: makes the pending mutations visible
+share_commit(_S) -> ?NOT_LOADED.
+%% share_pick(S, [{Topic, Group, erlang:phash2(ClientId), erlang:phash2(SourceTopic),
+%%                 Draw :: 0..16#FFFFFFFF, RoundRobinState | undefined}]) ->
+%%     [{picked | no_subscribers | host_strategy, Sub | undefined, RoundRobinState | undefined,
+%%       Count}]: pick/6 for a first dispatch per request; the state returned is stored back into
+%%     {shared_sub_round_robin, Group, Topic}; host_strategy (sticky) is picked by the caller
+%%     from share_members/3
+share_pick(_S, _Requests) -> ?NOT_LOADED.
+%% share_members(S, Group, Topic) -> [{Sub, Local :: boolean()}]: subscribers/2, in order
+share_members(_S, _Group, _Topic) -> ?NOT_LOADED.
+%% share_close(S) -> ok
+share_close(_S) -> ?NOT_LOADED.
 %% snapshot_save(Res, Path :: binary()) -> ok | {error, Reason}: the committed index to a file
 snapshot_save(_Res, _Path) -> ?NOT_LOADED.
 %% snapshot_load(Res, Path :: binary()) -> ok | {error, Reason}: into a fresh resource, no build
