@@ -222,10 +222,19 @@ constexpr uint32_t VINL = 60;
 // and wbase only for levels from REC_TOKS on.  With fewer than REC_U4 parts the header word
 // n_words | flags << 24 travels in a u32 per topic beside the records (Scratch::hdr), the
 // block stride stays REC_U4 parts, and the walk takes the tokens not stored as 0.
+// The even-elided form (r17; a pass over an index whose literal edges of level 0, and those of
+// level 2, each carry at most one token c_k != 0: `site/<id>/device/<id>/...`): all the walk can
+// learn from word k of such a level is whether it equals c_k, so the record is two parts,
+//   {tok1, tok3} {tok4, tok5}
+// and the header word carries T_EQ0 / T_EQ2 (word k is present and its token is c_k).  The walk
+// rebuilds tok0 / tok2 as c_k or 0 when it activates the topic (rec_tokens_even): no edge of the
+// level carries 0, and only equality with edge tokens, bucket homes computed from them and
+// signature classes (which decide probes, never rows) depend on a level token.
 constexpr uint32_t REC_U4 = 4;
 constexpr uint32_t REC_BLOCK = 64;
 constexpr uint32_t REC_TOKS = 7;
-constexpr uint32_t REC_PARTS_MIN = 3;  // the walk has two record readers: 3 parts and all 4
+constexpr uint32_t REC_PARTS_MIN = 3;  // rec_parts' least: the walk's readers are 3 parts, all 4,
+                                       // and the even-elided form's 2 (REC_R3 / RFULL / REVEN below)
 template <class T>
 GM_HD T* rec_at(T* rec, uint32_t t) {
   return rec + (uint64_t)(t / REC_BLOCK) * (REC_BLOCK * REC_U4) + (t % REC_BLOCK);
@@ -264,5 +273,39 @@ GM_HD void rec_tokens(const U4& a, const U4& b, const U4& c, const U4& d, uint64
 }
 constexpr uint32_t T_WILD = 1u;    // some level is exactly '+' or '#'  -> trie result []
 constexpr uint32_t T_DOLLAR = 2u;  // first byte is '$' -> no root '+'/'#' (emqx_trie.erl:282)
+constexpr uint32_t T_EQ0 = 4u;     // even-elided records only: word 0 is there and its token is c_0,
+constexpr uint32_t T_EQ2 = 8u;     //   word 2 and c_2
+
+// The tokens of the literal edges of one level, as the host model keeps them for levels 0 and 2
+// (TrieModel::lev, DevIndex::lev_st): none, one (c_k != 0), many (or the one token is 0, the
+// empty word).  Delta commits only move it upwards.
+enum : uint32_t { LEV_NONE = 0, LEV_ONE = 1, LEV_MANY = 2 };
+// The record readers of k_walk (its REC template parameter): REC_PARTS_MIN parts and the header
+// array, all REC_U4 parts, or the two parts of the even-elided form and the header array.
+enum : uint32_t { REC_R3 = 0, REC_RFULL = 1, REC_REVEN = 2 };
+constexpr uint32_t REC_PARTS_EVEN = 2;
+
+// The even-elided form's load of topic t's record: parts {tok1, tok3} into a, {tok4, tok5} into
+// b, the header word into d.w; c and the rest of d keep what the caller put there (0).
+template <class U4>
+GM_HD void rec_load_even(const U4* rec, const uint32_t* hdr, uint32_t t, U4& a, U4& b, U4& d) {
+  const U4* q = rec_at(rec, t);
+  a = q[0];
+  b = q[REC_BLOCK];
+  d.w = hdr[t];
+}
+// Its level tokens: tok0 / tok2 rebuilt from the header's T_EQ0 / T_EQ2 and the pass's c0 / c2
+// (0: the level has no literal edge; the bit is clear then), tok6 reads 0.
+template <class U4>
+GM_HD void rec_tokens_even(const U4& a, const U4& b, uint32_t hd, uint64_t c0, uint64_t c2,
+                           uint64_t (&tk)[REC_TOKS]) {
+  tk[0] = ((hd >> 24) & T_EQ0) ? c0 : 0ull;
+  tk[1] = ((uint64_t)a.y << 32) | a.x;
+  tk[2] = ((hd >> 24) & T_EQ2) ? c2 : 0ull;
+  tk[3] = ((uint64_t)a.w << 32) | a.z;
+  tk[4] = ((uint64_t)b.y << 32) | b.x;
+  tk[5] = ((uint64_t)b.w << 32) | b.z;
+  tk[6] = 0ull;
+}
 
 }  // namespace gm

@@ -254,6 +254,9 @@ struct emqxgm {
   uint32_t ks_on = 1;              // keyed siblings share a loaded line (tune "keyed_share")
   uint32_t cb_on = 1;              // lookups end at closed buckets (tune "closed_buckets")
   uint32_t rec_parts_tune = 0;     // 0: record parts from the index's depth; 4: full records (tune "rec_parts")
+  // three-part passes take the even-elided form where they can (tune "rec_even"; written under
+  // mmu, read by pass_enqueue under emu: atomic)
+  std::atomic<uint32_t> rec_even_on{1};
   uint64_t census_depth[2 * CENSUS_DEPTHS] = {};  // the last census pass's loads per level
   uint8_t* d_in_bytes = nullptr;
   uint32_t* d_in_off = nullptr;
@@ -2050,6 +2053,18 @@ int pass_enqueue(emqxgm* h, PassCtx& c, const Epoch& E, const uint8_t* d_bytes,
   WalkGeom WG_ = (c.pipelined && !census) ? h->geom_pipe : h->geom;
   if (census) WG_.pair = 0;  // census walks are one lane per topic (their buffers count lanes)
   if (!s.fmt.pk) WG_.pair = 0;  // the pair walk stages packed only (gm_walk.inc put)
+  // the even-elided form (gm_common.h): three-part records whose words 0 and 2 can each only be
+  // compared with one token (or none), for a walk variant that has its reader.  Chosen here, in
+  // the copy both kernels read: a commit that adds a second token changes only later passes.
+  ix.rec_even = (h->rec_even_on.load(std::memory_order_relaxed) && ix.rec_parts == REC_PARTS_MIN && !ix.trie_empty &&
+                 ix.lev_st[0] != LEV_MANY && ix.lev_st[1] != LEV_MANY &&
+                 walk_reads_even(WG_, n, c.walk_level))
+                    ? 1u
+                    : 0u;
+  if (ix.rec_even) {
+    std::lock_guard<std::mutex> g(h->stmu);
+    h->st.even_passes += 1;
+  }
   const uint32_t stat = ix.trie_empty ? 0u : walk_static_chunks(WG_, n, c.walk_level, s.p_cap);
   roctx_mark(h->roctx, "k_tok");
   // (per-topic reject counts: only the verification passes write -- and then read -- them;
@@ -3612,6 +3627,7 @@ int emqxgm_snapshot_load(emqxgm_t* h, const char* path) {
   // not take the saved marks for its own (it would keep every key the table lost meanwhile)
   for (Filter& f : filters) f.sync_gen = 0;
   m.lone_rebuild();
+  m.lev_rebuild();
   // the closed-bucket bits and the slot owners are derived, like `lone`: an edge that is not on
   // its own chain (a lookup would never find it) or two edges in one slot fail the load
   if (!m.closed_rebuild()) {
@@ -4523,6 +4539,12 @@ int emqxgm_tune(emqxgm_t* h, const char* key, int64_t value) {
     if (value != 0 && value != (int64_t)REC_U4) return -EINVAL;
     std::lock_guard<std::mutex> g(h->mmu);
     h->rec_parts_tune = (uint32_t)value;
+    return 0;
+  }
+  if (strcmp(key, "rec_even") == 0) {  // 1: three-part passes take the even-elided form where they can
+    if (value < 0 || value > 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(h->mmu);
+    h->rec_even_on.store((uint32_t)value, std::memory_order_relaxed);
     return 0;
   }
   if (strcmp(key, "spin_us") == 0) {  // host pipes' waits poll before they block

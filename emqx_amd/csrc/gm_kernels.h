@@ -52,6 +52,13 @@ struct DevIndex {
   // topic-record parts a pass's k_tok stores and its k_walk loads (gm_common.h rec_parts); set
   // by the engine per pass from max_depth (tune "rec_parts"); REC_U4: full records
   uint32_t rec_parts = 4;
+  // the tokens of the literal edges of levels 0 and 2 ([0] / [1]): gm_common.h LEV_NONE / LEV_ONE
+  // (lev_tok, never 0) / LEV_MANY, from the host model (TrieModel::lev; not part of a snapshot)
+  uint32_t lev_st[2] = {2u, 2u};
+  uint64_t lev_tok[2] = {0, 0};
+  // 1: this pass moves even-elided records (gm_common.h: two parts, words 0 and 2 as header
+  // bits against lev_tok); set by the engine per pass beside rec_parts (tune "rec_even")
+  uint32_t rec_even = 0;
 };
 
 // Layout of the staged pairs of one pass.  Wide: {topic, filter, rank | REJ_BIT}, 12 B.  Packed
@@ -384,6 +391,11 @@ hipError_t launch_fanout(const DevIndex& ix, const Scratch& sc, FanScratch& fs, 
 uint32_t walk_blocks(const WalkGeom& g, uint32_t n, uint32_t level);
 // whether the walk of n topics runs two lanes per topic (k_walk PAIR)
 bool walk_pair(const WalkGeom& g, uint32_t n, uint32_t level);
+// whether that walk has the reader of even-elided records (gm_common.h REC_REVEN): the compact
+// one-lane-per-topic walks and their census variants, not the pair walk or the spilling one
+inline bool walk_reads_even(const WalkGeom& g, uint32_t n, uint32_t level) {
+  return WALK_CPT && level < WALK_SPILL && !walk_pair(g, n, level);
+}
 uint32_t walk_static_chunks(const WalkGeom& g, uint32_t n, uint32_t level, uint32_t pcap);
 // the claim counters' start values past the walk's static first claims (k_tok sets them)
 void walk_claim_init(const WalkGeom& g, uint32_t n, uint32_t level, uint32_t claim0[WALK_SHARDS]);

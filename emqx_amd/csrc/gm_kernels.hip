@@ -593,18 +593,29 @@ hipError_t launch_tok(const uint8_t* bytes, const uint32_t* off, uint32_t n, con
   a.wild_empty = ix.wild_empty;
   a.nt_rec = n >= TOK_NT_MIN;
   a.hdr = ix.rec_parts >= REC_U4 ? nullptr : sc.hdr;
+  const bool even = ix.rec_even && a.hdr;
+  a.c0 = ix.lev_st[0] == LEV_ONE ? ix.lev_tok[0] : 0ull;
+  a.c2 = ix.lev_st[1] == LEV_ONE ? ix.lev_tok[1] : 0ull;
   const dim3 grid(grid_for(n, 8192));
   const ExactArgs X = exact_args(ix, sc.xseq);
+#define GM_TOK(DEFER, CP)                                                              \
+  do {                                                                                 \
+    if (even)                                                                          \
+      hipLaunchKernelGGL((k_tok<DEFER, CP, true>), grid, dim3(WG), 0, s, a, X);        \
+    else                                                                               \
+      hipLaunchKernelGGL((k_tok<DEFER, CP, false>), grid, dim3(WG), 0, s, a, X);       \
+  } while (0)
   if (a.cp_bytes) {
     if (ix.plain_empty)
-      hipLaunchKernelGGL((k_tok<false, true>), grid, dim3(WG), 0, s, a, X);
+      GM_TOK(false, true);
     else
-      hipLaunchKernelGGL((k_tok<true, true>), grid, dim3(WG), 0, s, a, X);
+      GM_TOK(true, true);
   } else if (ix.plain_empty) {
-    hipLaunchKernelGGL((k_tok<false, false>), grid, dim3(WG), 0, s, a, X);
+    GM_TOK(false, false);
   } else {
-    hipLaunchKernelGGL((k_tok<true, false>), grid, dim3(WG), 0, s, a, X);
+    GM_TOK(true, false);
   }
+#undef GM_TOK
   return hipGetLastError();
 }
 
@@ -771,33 +782,50 @@ hipError_t launch_walk(const DevIndex& ix, Scratch& sc, uint32_t n, const WalkGe
   // the record reader: all REC_U4 parts, or REC_PARTS_MIN and the header array (rec_parts never
   // gives fewer; the pass's k_tok stored by the same ix.rec_parts)
   const bool full = ix.rec_parts >= REC_U4;
-#define GM_WALK(CENSUS, SPILL, STK, CPT, PAIR)                                                   \
-  do {                                                                                           \
-    if (full)                                                                                    \
-      hipLaunchKernelGGL((k_walk<CENSUS, SPILL, STK, CPT, PAIR, true>), grid, dim3(WG), 0, s, a);  \
-    else                                                                                         \
-      hipLaunchKernelGGL((k_walk<CENSUS, SPILL, STK, CPT, PAIR, false>), grid, dim3(WG), 0, s, a); \
+  // the even-elided form (the engine chose it for a walk that has its reader: walk_reads_even)
+  const bool even = !full && ix.rec_even;
+  if (even && (level >= WALK_SPILL || pair)) return hipErrorInvalidValue;
+  a.c0 = ix.lev_st[0] == LEV_ONE ? ix.lev_tok[0] : 0ull;
+  a.c2 = ix.lev_st[1] == LEV_ONE ? ix.lev_tok[1] : 0ull;
+#define GM_WALK_R(CENSUS, SPILL, STK, CPT, PAIR, REC) \
+  hipLaunchKernelGGL((k_walk<CENSUS, SPILL, STK, CPT, PAIR, REC>), grid, dim3(WG), 0, s, a)
+#define GM_WALK(CENSUS, SPILL, STK, CPT, PAIR)                \
+  do {                                                        \
+    if (full)                                                 \
+      GM_WALK_R(CENSUS, SPILL, STK, CPT, PAIR, REC_RFULL);    \
+    else                                                      \
+      GM_WALK_R(CENSUS, SPILL, STK, CPT, PAIR, REC_R3);       \
+  } while (0)
+  // (the variants built with the even-elided reader as well)
+#define GM_WALK_E(CENSUS, STK, CPT)                           \
+  do {                                                        \
+    if (even)                                                 \
+      GM_WALK_R(CENSUS, false, STK, CPT, false, REC_REVEN);   \
+    else                                                      \
+      GM_WALK(CENSUS, false, STK, CPT, false);                \
   } while (0)
   if (census) {
     if (level >= WALK_SPILL)
       GM_WALK(true, true, SP, false, false);
     else if (level == WALK_DEEP)
-      GM_WALK(true, false, DP, C, false);
+      GM_WALK_E(true, DP, C);
     else
-      GM_WALK(true, false, SH, C, false);
+      GM_WALK_E(true, SH, C);
   } else {
     if (level >= WALK_SPILL)
       GM_WALK(false, true, SP, false, false);
     else if (level == WALK_DEEP && pair)
       GM_WALK(false, false, DP, C, true);
     else if (level == WALK_DEEP)
-      GM_WALK(false, false, DP, C, false);
+      GM_WALK_E(false, DP, C);
     else if (pair)
       GM_WALK(false, false, SH, C, true);
     else
-      GM_WALK(false, false, SH, C, false);
+      GM_WALK_E(false, SH, C);
   }
+#undef GM_WALK_E
 #undef GM_WALK
+#undef GM_WALK_R
   return hipGetLastError();
 }
 

@@ -228,6 +228,15 @@ struct TrieModel {
   std::vector<uint32_t> multi;  // [count, fid...] lists of nodes shared by several filters
   bool needs_verify = false;
   uint32_t max_depth = 0;
+  // The tokens the walk can compare a topic's word 0 ([0]) and word 2 ([1]) against: those of the
+  // literal edges of that level under any parent (keyed edges, fat halves and the root's carried
+  // slots are nodes like the rest; a `tn` key of level 0 hangs off such an edge).  A state
+  // (gm_common.h LEV_NONE / LEV_ONE / LEV_MANY) and, for LEV_ONE, the token: exact after a full
+  // build and a snapshot load (lev_rebuild), only ever raised by delta commits (a deletion
+  // leaves it, as with `sig` and `hcode`).  Token 0, the empty word, counts as many: the walk
+  // reads a word that differs from the one token as 0.  Not part of a snapshot.
+  uint32_t lev_st[2] = {LEV_NONE, LEV_NONE};
+  uint64_t lev_tok[2] = {0, 0};
   uint64_t n_trie = 0, n_route = 0;
   uint64_t n_nodes0 = 0, fv_words0 = 0;  // nodes / verify words at the build (headroom used since)
   // exact route keys: entry per committed key, bitmaps over entries.  Two regions of one
@@ -413,6 +422,10 @@ struct TrieModel {
     root_plus_half(x);
     x.needs_verify = needs_verify;
     x.max_depth = max_depth;
+    for (uint32_t i = 0; i < 2; ++i) {
+      x.lev_st[i] = lev_st[i];
+      x.lev_tok[i] = lev_st[i] == LEV_ONE ? lev_tok[i] : 0ull;
+    }
     x.fid_bound = (uint64_t)fv_cap * 32;
     x.trie_empty = (n_trie == 0);
     x.plain_empty = (n_route_p == 0);
@@ -421,11 +434,34 @@ struct TrieModel {
   bool lone_parent(uint32_t par) const {  // a depth-2 '+' node
     return par != 0 && tok[par] == PLUS_TOK && parent[par] != 0 && parent[parent[par]] == 0;
   }
+  // the level (0 or 2, as an index of lev_st) whose words node par's literal children are
+  // compared against, or 2: another level
+  uint32_t lev_index(uint32_t par) const {
+    if (par == 0) return 0;
+    return parent[par] != 0 && parent[parent[par]] == 0 ? 1u : 2u;
+  }
+  void lev_note(uint32_t par, uint64_t t) {  // a literal edge (par, t): none -> one -> many
+    const uint32_t i = lev_index(par);
+    if (i >= 2 || lev_st[i] == LEV_MANY) return;
+    if (t == 0 || (lev_st[i] == LEV_ONE && lev_tok[i] != t)) {
+      lev_st[i] = LEV_MANY;
+    } else {
+      lev_st[i] = LEV_ONE;
+      lev_tok[i] = t;
+    }
+  }
+  void lev_rebuild() {  // from the node arrays (a snapshot load)
+    lev_st[0] = lev_st[1] = LEV_NONE;
+    lev_tok[0] = lev_tok[1] = 0;
+    for (uint32_t c = 1; c < parent.size(); ++c)
+      if (slot[c] != DEAD && tok[c] != PLUS_TOK) lev_note(parent[c], tok[c]);
+  }
   void child_added(uint32_t par, uint32_t c) {  // new_node: c hangs under par
     if (tok[c] == PLUS_TOK) {
       pchild[par] = c;
       return;
     }
+    lev_note(par, tok[c]);
     nlit[par] += 1;
     sig[par] |= (uint8_t)sig_bit(tok[c]);
     if (!lone_parent(par)) return;

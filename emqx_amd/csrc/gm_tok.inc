@@ -85,6 +85,10 @@ struct TokArgs {
   bool nt_rec;  // records stored non-temporally (batches of at least TOK_NT_MIN topics)
   uint32_t* hdr;  // null: all REC_U4 record parts are stored (gm_common.h rec_parts); else
                   // REC_PARTS_MIN, and the header word n_words | flags << 24 of topic t at hdr[t]
+  // the even-elided form (gm_common.h; k_tok's EVEN instantiations, hdr set): parts {tok1, tok3}
+  // {tok4, tok5}, and T_EQ0 / T_EQ2 in the header word for a word 0 / 2 whose token is c0 / c2
+  // (0: the level has no token).  The other instantiations never read them.
+  uint64_t c0, c2;
 };
 
 // Batches from which k_tok stores its records non-temporally: 128 MB of records and up do not
@@ -336,13 +340,35 @@ __device__ __forceinline__ uint32_t tok_words_rec(const uint32_t* w, uint32_t s,
 
 // Topic t's record (gm_common.h rec_at): all REC_U4 parts {tok0, tok1} {tok2, tok3} {tok4, tok5}
 // {tok6, wbase, header}, or (A.hdr set) the first REC_PARTS_MIN and the header word to hdr[t]
-// (lanes of consecutive topics fill whole lines there too).  Non-temporal for large batches
+// (lanes of consecutive topics fill whole lines there too), or (EVEN) the even-elided form's
+// two parts {tok1, tok3} {tok4, tok5} and the header word with T_EQ0 / T_EQ2: 44 B per topic
+// with nw and exact_id instead of 60.  (EVEN is a template parameter, of k_tok too: as a
+// run-time branch it took k_tok<0,0> from 62 to 65 VGPRs, past the 64 at which two of its waves
+// fit a SIMD beside three of the walk's, and the pipelined cfg3 step lost 2%: MEASUREMENTS r17.)
+// Non-temporal for large batches
 // (nt_rec: records are read back once, by the walk, and would evict its edges).
+template <bool EVEN = false>
 __device__ __forceinline__ void store_rec(const TokArgs& A, uint32_t t, const uint64_t (&tk)[REC_TOKS],
                                           uint32_t wb, uint32_t hd) {
   uint4* q = rec_at(A.rec, t);
   constexpr uint32_t S = REC_BLOCK;
   const bool full = A.hdr == nullptr;  // (wave-uniform)
+  if constexpr (EVEN) {  // two parts, words 0 and 2 as a bit each in the header word
+    hd |= (A.c0 != 0 && tk[0] == A.c0 ? T_EQ0 << 24 : 0u) | (A.c2 != 0 && tk[2] == A.c2 ? T_EQ2 << 24 : 0u);
+    const uint4 e0 = make_uint4((uint32_t)tk[1], (uint32_t)(tk[1] >> 32), (uint32_t)tk[3], (uint32_t)(tk[3] >> 32));
+    const uint4 e1 = make_uint4((uint32_t)tk[4], (uint32_t)(tk[4] >> 32), (uint32_t)tk[5], (uint32_t)(tk[5] >> 32));
+    if (A.nt_rec) {
+      typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+      __builtin_nontemporal_store(u4v{e0.x, e0.y, e0.z, e0.w}, (u4v*)q);
+      __builtin_nontemporal_store(u4v{e1.x, e1.y, e1.z, e1.w}, (u4v*)(q + S));
+      __builtin_nontemporal_store(hd, A.hdr + t);
+    } else {
+      q[0] = e0;
+      q[S] = e1;
+      A.hdr[t] = hd;
+    }
+    return;
+  }
   const uint4 r0 = make_uint4((uint32_t)tk[0], (uint32_t)(tk[0] >> 32), (uint32_t)tk[1], (uint32_t)(tk[1] >> 32));
   const uint4 r1 = make_uint4((uint32_t)tk[2], (uint32_t)(tk[2] >> 32), (uint32_t)tk[3], (uint32_t)(tk[3] >> 32));
   const uint4 r2 = make_uint4((uint32_t)tk[4], (uint32_t)(tk[4] >> 32), (uint32_t)tk[5], (uint32_t)(tk[5] >> 32));
@@ -372,7 +398,8 @@ __device__ __forceinline__ void store_rec(const TokArgs& A, uint32_t t, const ui
 // region there).  Otherwise a wildcard name probes the wildcard-key region here (rare).
 // CP = copy-through (TokArgs cp_*): its own instantiation -- the extra stores in the default
 // kernel cost the cfg3 tokenizer 35% (r04: 0.087 -> 0.117 ms)
-template <bool DEFER, bool CP>
+// EVEN = the pass moves even-elided records (store_rec).
+template <bool DEFER, bool CP, bool EVEN = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_tok(TokArgs A, ExactArgs X) {
   __shared__ uint4 s_buf[TILE_CHUNKS];
   const uint32_t tid = threadIdx.x;
@@ -420,7 +447,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_
       __syncthreads();  // every lane is done with the tile's bytes
       if (t < t1) {
         A.nw[t] = nwd;
-        store_rec(A, t, tk, wb, nwd | (flags << 24));
+        store_rec<EVEN>(A, t, tk, wb, nwd | (flags << 24));
         if (flags & T_WILD) {
           if (DEFER)
             hit = X_WILDPEND;
@@ -454,7 +481,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_
       const uint32_t nwd = tok_words(P, len, A.test_mask, dst, flags);
       A.nw[t] = nwd;
       const uint64_t tk[REC_TOKS] = {tk0, tk1, tk2, tk3, tk4, tk5, tk6};
-      store_rec(A, t, tk, wb, nwd | (flags << 24));
+      store_rec<EVEN>(A, t, tk, wb, nwd | (flags << 24));
       if (flags & T_WILD) {
         if (DEFER)
           hit = X_WILDPEND;

@@ -84,6 +84,8 @@ struct WalkArgs {
                         // gm_common.h slot_closed)
   unsigned long long* census;  // [0] states, [1] slot loads, [2] lane iters, [3] wave iters,
                                // then per wave {start, claims exhausted, end} (wall clock)
+  uint64_t c0, c2;      // the even-elided reader (REC_REVEN): the one token of the literal edges
+                        // of level 0 / level 2, 0: none (read in the activation block only)
 };
 
 // Topic t's 64-B record (gm_common.h rec_at): lanes holding consecutive topics load whole lines
@@ -92,13 +94,18 @@ struct WalkArgs {
 // measured slower (profiles/r05/ab_nt).
 // (One address and the parts at immediate offsets of 1 KB: a separate 64-bit address per part,
 // for a fully part-major layout, cost the walk 6 VGPRs, past 128.)
-// FULLREC (a k_walk template parameter): the pass stored all REC_U4 parts; otherwise
-// REC_PARTS_MIN parts and the header word in A.hdr (gm_common.h rec_parts, rec_load) -- one line
-// per 64 topics less to request, and the registers of tok6 and wbase are constants.
-template <bool FULLREC>
+// REC (a k_walk template parameter, gm_common.h REC_R*): REC_RFULL, the pass stored all REC_U4
+// parts; REC_R3, REC_PARTS_MIN parts and the header word in A.hdr (gm_common.h rec_parts,
+// rec_load) -- one line per 64 topics less to request, and the registers of tok6 and wbase are
+// constants; REC_REVEN, the even-elided form's two parts and the header word (rec_load_even) --
+// another line less, and one prefetched uint4 (c) stays a constant.
+template <uint32_t REC>
 __device__ __forceinline__ void load_rec(const WalkArgs& A, uint32_t t, uint4& a, uint4& b, uint4& c,
                                          uint4& d) {
-  rec_load<FULLREC>(A.rec, A.hdr, t, a, b, c, d);
+  if constexpr (REC == REC_REVEN)
+    rec_load_even(A.rec, A.hdr, t, a, b, d);
+  else
+    rec_load<REC == REC_RFULL>(A.rec, A.hdr, t, a, b, c, d);
 }
 
 struct WaveOut {  // wave-uniform cursor into this wave's reserved chunk of staged pairs
@@ -402,8 +409,9 @@ __device__ __forceinline__ uint32_t pair_xchg(uint32_t v) {
 // Only slot 0 anchors a shared line: its fields are read at a constant index (a select between
 // two P[] fields puts the array into scratch).  A slot that has moved along a chain is not at an
 // item's home and shares nothing.
-template <bool CENSUS, bool SPILL, uint32_t STK, bool CPT = false, bool PAIR = false, bool FULLREC = true>
+template <bool CENSUS, bool SPILL, uint32_t STK, bool CPT = false, bool PAIR = false, uint32_t REC = REC_RFULL>
 __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
+  static_assert(REC != REC_REVEN || (!SPILL && !PAIR), "the even-elided reader: the one-lane LDS-only walks");
   static_assert(!(CPT && SPILL), "compact items live in LDS only");
   static_assert(!PAIR || (CPT && !SPILL && !CENSUS), "pairs: the compact LDS-only production walk");
   constexpr uint32_t NS = PAIR ? PAIR_WSLOTS : WSLOTS;  // probe slots per lane
@@ -490,7 +498,10 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         t = NONE;
       } else {
         uint64_t tk[REC_TOKS];
-        rec_tokens(nr0, nr1, nr2, nr3, tk);
+        if constexpr (REC == REC_REVEN)  // tok0 / tok2 from their header bits: c_k or 0
+          rec_tokens_even(nr0, nr1, nr3.w, A.c0, A.c2, tk);
+        else
+          rec_tokens(nr0, nr1, nr2, nr3, tk);
         L.cls = 0;
 #pragma unroll
         for (uint32_t k = 0; k < REC_TOKS; ++k) {
@@ -511,7 +522,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
     if (A.static_one && !done) {
       if ((PAIR ? L.gl >> 1 : L.gl) < A.n) {
         nxt = PAIR ? L.gl >> 1 : L.gl;
-        load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);
+        load_rec<REC>(A, nxt, nr0, nr1, nr2, nr3);
       }
       done = true;
     }
@@ -555,7 +566,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
       const uint32_t r = mbcnt64(mi);
       if (lead && nxt == NONE && r < avail) {
         nxt = q_next + r;
-        load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);  // consumed when this lane next idles
+        load_rec<REC>(A, nxt, nr0, nr1, nr2, nr3);  // consumed when this lane next idles
       }
       q_next += min((uint32_t)__popcll(mi), avail);
       mi = __ballot(lead && nxt == NONE);
@@ -565,7 +576,7 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
         const uint32_t ln = pair_xchg(nxt);
         if (!lead && nxt == NONE && ln != NONE) {
           nxt = ln;
-          load_rec<FULLREC>(A, nxt, nr0, nr1, nr2, nr3);
+          load_rec<REC>(A, nxt, nr0, nr1, nr2, nr3);
         }
       }
     }
@@ -860,9 +871,13 @@ __global__ __launch_bounds__(WG) void k_walk(WalkArgs A) {
     // The prefetched record and every slot's data (an idle slot's dummy load included) are
     // complete by now; saying so keeps the compiler from draining vmcnt (stores included)
     // wherever it later reuses those registers.
-    asm volatile("" ::"v"(nr0.x), "v"(nr0.y), "v"(nr0.z), "v"(nr0.w), "v"(nr1.x), "v"(nr1.y),
-                 "v"(nr1.z), "v"(nr1.w), "v"(nr2.x), "v"(nr2.y), "v"(nr2.z), "v"(nr2.w),
-                 "v"(nr3.x), "v"(nr3.y), "v"(nr3.z), "v"(nr3.w));
+    if constexpr (REC == REC_REVEN)  // (nr2 and the rest of nr3 are never loaded: constants)
+      asm volatile("" ::"v"(nr0.x), "v"(nr0.y), "v"(nr0.z), "v"(nr0.w), "v"(nr1.x), "v"(nr1.y),
+                   "v"(nr1.z), "v"(nr1.w), "v"(nr3.w));
+    else
+      asm volatile("" ::"v"(nr0.x), "v"(nr0.y), "v"(nr0.z), "v"(nr0.w), "v"(nr1.x), "v"(nr1.y),
+                   "v"(nr1.z), "v"(nr1.w), "v"(nr2.x), "v"(nr2.y), "v"(nr2.z), "v"(nr2.w),
+                   "v"(nr3.x), "v"(nr3.y), "v"(nr3.z), "v"(nr3.w));
 #pragma unroll
     for (uint32_t j = 0; j < NS; ++j)
       asm volatile("" ::"v"(P[j].s0.x), "v"(P[j].s1.x), "v"(P[j].s0.w), "v"(P[j].s1.w),

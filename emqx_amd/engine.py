@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 10  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 11  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -131,7 +131,8 @@ class _Stats(C.Structure):
                 ("exact_ms", C.c_double), ("keyed_nodes", C.c_uint64),
                 ("buffer_grows", C.c_uint64), ("sync_gathers", C.c_uint64),
                 ("bg_builds", C.c_uint64), ("bg_waits", C.c_uint64),
-                ("last_build_ms", C.c_double), ("catchup_changes", C.c_uint64)]
+                ("last_build_ms", C.c_double), ("catchup_changes", C.c_uint64),
+                ("even_passes", C.c_uint64)]
 
 
 # name -> (restype, argtypes): exactly the entry points declared in include/emqx_gpumatch.h

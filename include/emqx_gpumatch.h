@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 10
+#define EMQXGM_ABI_VERSION 11
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -146,6 +146,7 @@ typedef struct emqxgm_stats {
                                their delta */
   double last_build_ms;     /* wall time of the last full build (background: start to ready) */
   uint64_t catchup_changes; /* filters replayed onto the last background build at its install */
+  uint64_t even_passes;     /* passes enqueued with even-elided topic records (tune "rec_even") */
 } emqxgm_stats;
 
 int emqxgm_abi_version(void);
@@ -1020,6 +1021,12 @@ int emqxgm_set_profiling(emqxgm_t* h, int on);
  * each 64-B topic record that the committed index can read -- three of four, and a 4-B header
  * word, while no trie filter has 7 levels or more; 4: full records always -- an A/B
  * switch from the next pass on, same rows, same order, every walk variant and the census);
+ * "rec_even" (1 default: a three-part pass over an index whose literal edges of level 0, and those
+ * of level 2, each carry at most one token (`site/<id>/device/<id>/...`) moves even-elided records,
+ * two parts {tok1, tok3} {tok4, tok5} and a header bit for each of the words 0 and 2, DESIGN.md 3,
+ * where its walk has the reader: the one-lane-per-topic walks and the census, not the pair walk
+ * or the spilling one; 0: three parts -- an A/B switch from the next pass on, same rows;
+ * emqxgm_stats::even_passes counts the passes enqueued in the form; "rec_parts" 4 overrides it);
  * "host_out" (host pipes copy results to the
  * host with hipMemcpyAsync, 0 default, or with a kernel writing host memory, 1);
  * "walk_pair" (1 default: a batch of at most half the walk grid's lanes is walked by two lanes
