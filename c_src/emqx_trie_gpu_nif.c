@@ -24,9 +24,14 @@
  * subscribers/3, register/3 and set_local_node/2 (the fan-out tables, the terms behind their
  * handles), and route_set_many/3 + sync_begin/1 + sync_end/2 + commit/1 for a resync.
  *
- * Compiled only where erl_nif.h exists (c_src/Makefile); this image has no Erlang runtime, so
- * the C-ABI below it is tested through ctypes and the C harness of tests/host_harness
- * (tests/test_gpu_async.py drives emqxgm_async_* from 16 and 64 threads as publishers do).
+ * Compiled for a broker only where erl_nif.h exists (c_src/Makefile).  The tests have no Erlang
+ * runtime: they link this file against a small erl_nif runtime of their own (tests/nif_stub:
+ * interned atoms, terms owned by their environment, counted resources, mailboxes) and run it from
+ * tests/host_harness/nif_driver.c -- on the CPU under ASan + UBSan and TSan over the real async
+ * layer and a mock engine (tests/test_nif_host.py: every entry, malformed arguments, error
+ * returns, publishers racing cancels), and on the device over the engine (tests/test_gpu_nif.py),
+ * against the Python references.  Not covered there: BEAM's scheduling, the cost of its term
+ * copies, and on_load in a broker.
  */
 #include <erl_nif.h>
 #include <errno.h>
@@ -248,7 +253,10 @@ static ERL_NIF_TERM nif_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]
   ERL_NIF_TERM list = argv[0], head, pub, eag;
   ErlNifSInt64 spin, bg, rth, fth;
   (void)argc;
-  if (!enif_get_list_length(env, list, &ndev) || ndev == 0 || ndev > GM_MAX_DEVICES ||
+  /* Opts must be a map (a put into anything else fails): enif_get_map_value below would read a
+   * non-map as "no option given" */
+  if (!enif_make_map_put(env, argv[5], A_OK, A_OK, &head) ||
+      !enif_get_list_length(env, list, &ndev) || ndev == 0 || ndev > GM_MAX_DEVICES ||
       !enif_get_uint(env, argv[1], &wt) || !enif_get_uint(env, argv[2], &wb) ||
       !enif_get_uint(env, argv[3], &wus) || !enif_get_uint(env, argv[4], &ml) ||
       !opt_uint(env, argv[5], A_SPIN_US, 0, &spin) || !opt_uint(env, argv[5], A_BG_BUILD, 16384, &bg) ||
@@ -625,8 +633,10 @@ static ERL_NIF_TERM nif_subscribers(ErlNifEnv* env, int argc, const ERL_NIF_TERM
 static ERL_NIF_TERM nif_register(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   gm_res* r;
   ERL_NIF_TERM head, l = argv[2];
+  unsigned len;
   (void)argc;
-  if (!get_res(env, argv[0], &r) || !enif_is_list(env, argv[2])) return enif_make_badarg(env);
+  /* a proper list: an improper one would register its head and answer ok */
+  if (!get_res(env, argv[0], &r) || !enif_get_list_length(env, argv[2], &len)) return enif_make_badarg(env);
   term_tab* t = argv[1] == A_NODE ? &r->nodes : argv[1] == A_GROUP ? &r->groups : argv[1] == A_SUB ? &r->subs : NULL;
   if (!t) return enif_make_badarg(env);
   int bad = 0;
@@ -1229,6 +1239,9 @@ static ERL_NIF_TERM nif_retain_match_limit(ErlNifEnv* env, int argc, const ERL_N
   }
   if (!rc) {
     ERL_NIF_TERM ll = argv[3], cl = argv[4], h;
+    unsigned nl, nc; /* one limit and one cursor per filter, in proper lists */
+    if (!enif_get_list_length(env, ll, &nl) || !enif_get_list_length(env, cl, &nc) || nl != p.n || nc != p.n)
+      rc = -EINVAL;
     for (unsigned i = 0; !rc && i < p.n; ++i) {
       unsigned l;
       ErlNifBinary cb;
@@ -1315,7 +1328,7 @@ static ERL_NIF_TERM nif_retain_page_read(ErlNifEnv* env, int argc, const ERL_NIF
   if (!get_retain(env, argv[0], &g) || !enif_get_uint64(env, argv[2], &page) ||
       !enif_get_uint64(env, argv[3], &limit) || !enif_get_uint64(env, argv[4], &now))
     return enif_make_badarg(env);
-  const int all = enif_is_atom(env, argv[1]);
+  const int all = argv[1] == A_UNDEFINED; /* no other atom stands for "every topic" */
   if (!all && !enif_inspect_binary(env, argv[1], &b)) return enif_make_badarg(env);
   if (!all && b.size > GM_MAX_TOPIC) return enif_make_list(env, 0);
   const uint32_t* ids = NULL;

@@ -8,6 +8,8 @@
 * ``tests/host_harness/lib/libasync_load.so`` -- publisher threads driving the engine's concurrent
   entry (tests/host_harness/async_load.cpp; test and bench infrastructure, linked against the
   engine).
+* ``tests/host_harness/lib/nif_driver`` -- the NIF on the fake erl_nif runtime of tests/nif_stub,
+  linked against the engine (tests/host_harness/nif_driver.c; test infrastructure).
 
 Outputs are git-ignored and travel to the GPU box with the tree.
 """
@@ -24,6 +26,7 @@ ENGINE_SO = os.path.join(ROOT, "emqx_amd", "libemqx_gpumatch.so")
 ORACLE_SO = os.path.join(ROOT, "oracle", "build", "libemqx_ref.so")
 WORKLOAD_SO = os.path.join(ROOT, "workloads", "libemqx_workload.so")
 LOAD_SO = os.path.join(ROOT, "tests", "host_harness", "lib", "libasync_load.so")
+NIF_DRIVER = os.path.join(ROOT, "tests", "host_harness", "lib", "nif_driver")
 
 ENGINE_SRCS = ["gm_kernels.hip", "gm_engine.cpp", "gm_retain.cpp", "gm_ruleset.cpp", "gm_acl.cpp", "gm_acldb.cpp", "gm_share.cpp", "gm_batcher.cpp", "gm_async.cpp"]
 ENGINE_DEPS = sorted(set(ENGINE_SRCS) | {f for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))})
@@ -88,9 +91,27 @@ def build_load_harness(force: bool = False) -> str:
     return LOAD_SO
 
 
+def build_nif_driver(force: bool = False) -> str:
+    """The NIF (c_src/emqx_trie_gpu_nif.c, compiled as C) on the fake erl_nif runtime, linked
+    against the engine: the program tests/test_gpu_nif.py runs on the device."""
+    srcs = [os.path.join(ROOT, "c_src", "emqx_trie_gpu_nif.c"),
+            os.path.join(ROOT, "tests", "nif_stub", "fake_erl_nif.c"),
+            os.path.join(ROOT, "tests", "host_harness", "nif_driver.c")]
+    stub = os.path.join(ROOT, "tests", "nif_stub")
+    deps = srcs + [ENGINE_SO, os.path.join(ROOT, "include", "emqx_gpumatch.h"),
+                   os.path.join(stub, "erl_nif.h"), os.path.join(stub, "fake_erl_nif.h")]
+    if force or _stale(NIF_DRIVER, deps):
+        os.makedirs(os.path.dirname(NIF_DRIVER), exist_ok=True)
+        _run(["gcc", "-O2", "-std=gnu11", "-pthread", "-Wall", "-I", stub,
+              "-I", os.path.join(ROOT, "include")] + srcs +
+             ["-L", os.path.dirname(ENGINE_SO), "-l:libemqx_gpumatch.so",
+              "-Wl,-rpath,$ORIGIN/../../../emqx_amd", "-Wl,--allow-shlib-undefined", "-o", NIF_DRIVER])
+    return NIF_DRIVER
+
+
 def build_all(force: bool = False):
     return (build_engine(force), build_oracle(force), build_workloads(force),
-            build_load_harness(force))
+            build_load_harness(force), build_nif_driver(force))
 
 
 if __name__ == "__main__":

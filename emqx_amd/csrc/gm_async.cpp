@@ -597,6 +597,11 @@ struct emqxgm_async {
       w.flush_ns = s.flush_ns;
       w.done_ns = done;
       deliver(w);
+      // The reported calls' tags go with the report.  Left in place, a cancel() of a call that
+      // was already answered could find its tag again in the slot's next use, in a place another
+      // caller has reserved but not written yet, and return 1 for a call that was reported: its
+      // owner then lets the call go a second time.
+      for (uint32_t j = 0; j < s.n; ++j) s.tag[j].store(EMQXGM_TAG_CANCELLED, std::memory_order_relaxed);
       g.lock();
       st_delivered += s.n;
       if (rc) st_errors += 1;

@@ -337,7 +337,7 @@ int ref_match_batch(void* h, const uint8_t* tb, const uint32_t* toff, uint64_t n
   uint32_t* ids = (uint32_t*)malloc(std::max<uint64_t>(total, 1) * 4);
   uint64_t pos = 0;
   for (int w = 0; w < threads; ++w) {
-    memcpy(ids + pos, part[w].data(), part[w].size() * 4);
+    if (!part[w].empty()) memcpy(ids + pos, part[w].data(), part[w].size() * 4);
     pos += part[w].size();
   }
   *ids_out = ids;

@@ -2,13 +2,10 @@
 // gm_async.cpp) under ThreadSanitizer / AddressSanitizer on the CPU.
 //
 // gm_async.cpp is a layer over four engine entry points (emqxgm_host_alloc / _free,
-// emqxgm_match_batch_submit_filters / _wait_filters).  Here they are a mock engine whose
-// "device pass" is the oracle's C++ restatement of emqx_trie:match/1 + the route-key lookup
-// (oracle/ref_trie.cpp, emqx_trie.erl:282-348, emqx_router.erl:141-146), with the real engine's
-// contract enforced: at most EMQXGM_HOST_PIPES tickets in flight per handle (-EBUSY beyond), a
-// result's buffers valid only until ticket + EMQXGM_HOST_PIPES is submitted (the mock then
-// poisons them, so a layer that reads a released result reports garbage and fails the check),
-// and waits that take a random while.
+// emqxgm_match_batch_submit_filters / _wait_filters).  Here they are the mock engine of
+// mock_engine.h (shared with nif_driver_mock.cpp), whose "device pass" is the oracle's C++
+// restatement of emqx_trie:match/1 + the route-key lookup, with the real engine's pipe contract
+// enforced.
 //
 // T publisher threads call emqxgm_async_match one topic at a time with a bounded number of
 // calls outstanding each (their "processes"), cancel some of them, and check in the callback:
@@ -34,111 +31,9 @@
 #include "../../include/emqx_gpumatch.h"
 #include "../../emqx_amd/csrc/gm_internal.h"
 
-extern "C" {
-void* ref_create(int compact);
-void ref_destroy(void* h);
-int ref_add_many(void* h, const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint8_t* kind);
-int ref_match_batch(void* h, const uint8_t* tb, const uint32_t* toff, uint64_t n, int threads,
-                    uint64_t* row, uint32_t** ids_out, uint64_t* n_ids, uint32_t* exact);
-void ref_free(void* p);
-}
-
-#define CHECK(c, ...)                                             \
-  do {                                                            \
-    if (!(c)) {                                                   \
-      fprintf(stderr, "FAIL %s:%d: %s: ", __FILE__, __LINE__, #c); \
-      fprintf(stderr, __VA_ARGS__);                               \
-      fprintf(stderr, "\n");                                      \
-      abort();                                                    \
-    }                                                             \
-  } while (0)
-
-namespace {
-
-std::vector<std::string> g_filters;  // oracle ids = registration order
-void* g_ref = nullptr;
-std::mutex g_ref_mu;  // ref_match_batch is a reader, but keep the oracle single-threaded
-
-struct MockPipe {
-  uint64_t ticket = 0;
-  int state = 0;  // 0 free / taken, 1 in flight
-  std::vector<uint32_t> row, fid, exact, foff;
-  std::vector<uint8_t> fb;
-};
-
-}  // namespace
-
-struct emqxgm {
-  std::mutex mu;
-  MockPipe p[EMQXGM_HOST_PIPES];
-  uint64_t next = 1;
-  std::atomic<uint64_t> busy{0};
-  std::atomic<int> stale{0};     // the engine's health mark (emqxgm_mark_stale)
-  std::atomic<int> hang_us{0};   // health mode: waits stall this long (a hung device)
-};
+#include "mock_engine.h"
 
 extern "C" {
-
-void* emqxgm_host_alloc(emqxgm_t*, uint64_t bytes) { return malloc(bytes ? bytes : 1); }
-int emqxgm_mark_stale(emqxgm_t* h, int) {
-  h->stale.store(1);
-  return 0;
-}
-void emqxgm_host_free(emqxgm_t*, void* p) { free(p); }
-
-int emqxgm_match_batch_submit_filters(emqxgm_t* h, const uint8_t* bytes, const uint32_t* off,
-                                      uint32_t n, uint64_t* ticket) {
-  if (h->stale.load()) return -ESTALE;  // the real engine refuses a stale index's windows
-  std::lock_guard<std::mutex> g(h->mu);
-  const uint64_t tk = h->next;
-  MockPipe& p = h->p[tk % EMQXGM_HOST_PIPES];
-  if (p.state == 1) {
-    h->busy++;
-    return -EBUSY;
-  }
-  // the previous result of this pipe is overwritten now: poison it first (a reader of a released
-  // result then sees garbage)
-  std::fill(p.row.begin(), p.row.end(), 0xDEADBEEFu);
-  std::fill(p.fid.begin(), p.fid.end(), 0xDEADBEEFu);
-  std::fill(p.foff.begin(), p.foff.end(), 0xDEADBEEFu);
-  std::fill(p.fb.begin(), p.fb.end(), (uint8_t)0xEE);
-  CHECK(off[0] == 0, "offsets[0]");
-  std::vector<uint64_t> row(n + 1);
-  uint32_t* ids = nullptr;
-  uint64_t nid = 0;
-  p.exact.assign(n, 0);
-  {
-    std::lock_guard<std::mutex> r(g_ref_mu);
-    ref_match_batch(g_ref, bytes, off, n, 1, row.data(), &ids, &nid, p.exact.data());
-  }
-  p.row.assign(row.begin(), row.end());
-  p.fid.assign(ids, ids + nid);
-  ref_free(ids);
-  p.foff.assign(1, 0);
-  p.fb.clear();
-  for (uint32_t id : p.fid) {
-    p.fb.insert(p.fb.end(), g_filters[id].begin(), g_filters[id].end());
-    p.foff.push_back((uint32_t)p.fb.size());
-  }
-  p.ticket = tk;
-  p.state = 1;
-  h->next += 1;
-  *ticket = tk;
-  return 0;
-}
-
-}  // extern "C"
-int gm_stale(emqxgm_t* h) { return h->stale.load(); }
-// the engine's buffers sized for the layer's windows (nothing to size in the mock)
-int gm_reserve_windows(emqxgm_t* h, uint32_t n, uint64_t) { return h && n ? 0 : -EINVAL; }
-// the layer's window submit (gm_engine.cpp skips the offsets check there; the mock checks them)
-int gm_submit_window(emqxgm_t* h, const uint8_t* bytes, const uint32_t* off, uint32_t n,
-                     uint64_t* ticket) {
-  for (uint32_t i = 0; i < n; ++i) CHECK(off[i + 1] >= off[i], "window offsets increase");
-  return emqxgm_match_batch_submit_filters(h, bytes, off, n, ticket);
-}
-extern "C" {
-
 // publish-mode layers (EMQXGM_ASYNC_PUBLISH) are checked on the GPU (tests/test_gpu_async.py)
 int emqxgm_publish_batch(emqxgm_t*, const uint8_t*, const uint32_t*, uint32_t, emqxgm_publish_out*) {
   return -EIO;
@@ -146,29 +41,6 @@ int emqxgm_publish_batch(emqxgm_t*, const uint8_t*, const uint32_t*, uint32_t, e
 int emqxgm_filters_copy(emqxgm_t*, const uint32_t*, uint64_t, uint8_t*, uint64_t, uint64_t*) {
   return -EIO;
 }
-
-std::atomic<int> g_hang{0};  // health mode: every wait blocks while set (a hung device)
-
-int emqxgm_match_batch_wait_filters(emqxgm_t* h, uint64_t ticket, emqxgm_batch_out* out,
-                                    const uint32_t** foff, const uint8_t** fbytes) {
-  // the "device" takes a while; the layer must not hold its own lock meanwhile
-  thread_local std::mt19937 rng(std::hash<std::thread::id>()(std::this_thread::get_id()));
-  std::this_thread::sleep_for(std::chrono::microseconds(rng() % 300));
-  while (g_hang.load()) std::this_thread::sleep_for(std::chrono::microseconds(200));
-  std::lock_guard<std::mutex> g(h->mu);
-  MockPipe& p = h->p[ticket % EMQXGM_HOST_PIPES];
-  if (ticket == 0 || p.ticket != ticket || p.state != 1) return -ENOENT;
-  p.state = 0;
-  out->n = (uint32_t)p.exact.size();
-  out->n_pairs = (uint32_t)p.fid.size();
-  out->row_ptr = p.row.data();
-  out->filter_id = p.fid.data();
-  out->exact_id = p.exact.data();
-  *foff = p.foff.data();
-  *fbytes = p.fb.data();
-  return 0;
-}
-
 }  // extern "C"
 
 namespace {
@@ -278,7 +150,13 @@ int health_main(unsigned seed, int threads, int handles, uint32_t window) {
           const auto t0 = std::chrono::steady_clock::now();
           while (c.reported.load() == 0 && std::chrono::steady_clock::now() - t0 < timeout)
             std::this_thread::sleep_for(std::chrono::microseconds(50));
-          if (c.reported.load()) continue;
+          if (c.reported.load()) {
+            // a caller whose timeout raced its answer cancels anyway: 0, the report was made (the
+            // call's tag must not be found again in a later use of its window slot)
+            CHECK(emqxgm_async_cancel(a, tag, k) == 0, "call %llu cancelled after its report",
+                  (unsigned long long)tag);
+            continue;
+          }
           const int cr = emqxgm_async_cancel(a, tag, k);  // timed out
           CHECK(cr == 0 || cr == 1, "cancel %d", cr);
           if (cr == 1) {

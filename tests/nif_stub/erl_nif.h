@@ -1,6 +1,12 @@
-/* Test infrastructure only: the declarations of the erl_nif calls c_src/emqx_trie_gpu_nif.c
- * uses, with OTP's signatures, so tests/test_nif_syntax.py can compile-check the NIF where no
- * Erlang runtime (and so no erl_nif.h) exists.  Never linked, never run. */
+/* Test infrastructure only: the erl_nif calls c_src/emqx_trie_gpu_nif.c uses, with OTP's
+ * signatures, where no Erlang runtime (and so no erl_nif.h) exists.  tests/test_nif_syntax.py
+ * compile-checks the NIF against these declarations; tests/nif_stub/fake_erl_nif.c implements
+ * them as a small runtime (interned atoms, heap terms owned by their environment, counted
+ * resources, mailboxes), and tests/host_harness/nif_driver.c runs the NIF on it: on the CPU under
+ * sanitizers (tests/test_nif_host.py) and against the engine on the device
+ * (tests/test_gpu_nif.py).  What the runtime adds beyond erl_nif is in fake_erl_nif.h. */
+#ifndef FAKE_ERL_NIF_DECLS_H
+#define FAKE_ERL_NIF_DECLS_H
 #include <stddef.h>
 typedef unsigned long ERL_NIF_TERM;
 typedef struct enif_environment_t ErlNifEnv;
@@ -31,7 +37,20 @@ ERL_NIF_TERM enif_make_resource(ErlNifEnv*, void*); ERL_NIF_TERM enif_make_tuple
 ERL_NIF_TERM enif_make_uint(ErlNifEnv*, unsigned);
 ErlNifResourceType* enif_open_resource_type(ErlNifEnv*, const char*, const char*, ErlNifResourceDtor*, ErlNifResourceFlags, ErlNifResourceFlags*);
 ErlNifPid* enif_self(ErlNifEnv*, ErlNifPid*); int enif_send(ErlNifEnv*, const ErlNifPid*, ErlNifEnv*, ERL_NIF_TERM);
-#define ERL_NIF_INIT(name, funcs, load, reload, upgrade, unload) void* nif_init_##name(void) { (void)funcs; (void)load; (void)upgrade; (void)unload; return 0; }
+/* What nif_init returns: the function table and load (reload, upgrade and unload are not run). */
+typedef struct {
+  const char* name;
+  int num_of_funcs;
+  ErlNifFunc* funcs;
+  int (*load)(ErlNifEnv*, void**, ERL_NIF_TERM);
+} ErlNifEntry;
+#define ERL_NIF_INIT(NAME, FUNCS, LOAD, RELOAD, UPGRADE, UNLOAD)                                      \
+  ErlNifEntry* nif_init(void);                                                                        \
+  ErlNifEntry* nif_init(void) {                                                                       \
+    static ErlNifEntry entry = {#NAME, (int)(sizeof(FUNCS) / sizeof(FUNCS[0])), FUNCS, LOAD};         \
+    (void)(RELOAD); (void)(UPGRADE); (void)(UNLOAD);                                                  \
+    return &entry;                                                                                    \
+  }
 typedef unsigned long ErlNifUInt64; typedef long ErlNifSInt64;
 ERL_NIF_TERM enif_make_tuple2(ErlNifEnv*, ERL_NIF_TERM, ERL_NIF_TERM);
 ERL_NIF_TERM enif_make_tuple3(ErlNifEnv*, ERL_NIF_TERM, ERL_NIF_TERM, ERL_NIF_TERM);
@@ -58,3 +77,4 @@ int enif_thread_join(ErlNifTid, void**);
 typedef struct ErlNifMutex ErlNifMutex;
 ErlNifMutex* enif_mutex_create(char*); void enif_mutex_destroy(ErlNifMutex*);
 void enif_mutex_lock(ErlNifMutex*); void enif_mutex_unlock(ErlNifMutex*);
+#endif

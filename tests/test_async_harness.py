@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = os.path.join(ROOT, "tests", "host_harness")
 SRCS = [os.path.join(H, "async_harness.cpp"), os.path.join(ROOT, "emqx_amd", "csrc", "gm_async.cpp"),
         os.path.join(ROOT, "oracle", "ref_trie.cpp")]
-DEPS = SRCS + [os.path.join(ROOT, "include", "emqx_gpumatch.h")]
+DEPS = SRCS + [os.path.join(ROOT, "include", "emqx_gpumatch.h"), os.path.join(H, "mock_engine.h")]
 CLANG = "/opt/rocm/llvm/bin/clang++"
 
 

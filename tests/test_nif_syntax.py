@@ -1,6 +1,7 @@
-"""The NIF (c_src/emqx_trie_gpu_nif.c) compiles: no Erlang runtime exists in this image, so it is
-checked with gcc -fsyntax-only against tests/nif_stub/erl_nif.h (the erl_nif declarations it
-uses, OTP's signatures) and include/emqx_gpumatch.h.  Warnings are errors."""
+"""The NIF (c_src/emqx_trie_gpu_nif.c) compiles without a warning: gcc -fsyntax-only -Wall -Wextra
+-Werror against tests/nif_stub/erl_nif.h (the erl_nif declarations it uses, OTP's signatures)
+and include/emqx_gpumatch.h.  The same header is the fake runtime's (tests/nif_stub/
+fake_erl_nif.c), on which tests/test_nif_host.py and tests/test_gpu_nif.py link and run the NIF."""
 import os
 import shutil
 import subprocess
