@@ -10,7 +10,8 @@
   local dispatches ``(To, Sub)`` of the entries ``{To, node()}`` (dispatch/2, :326-355).
 * ``publish_shared_batch([Topic], [Message])`` -- the ``{To, Group}`` entries of the same answer
   handed to ``emqx_shared_sub:dispatch/3`` (:270-275): the member each one goes to, picked on the
-  device from ``Broker.shared`` (``emqx_amd.shared_sub.SharedSubs``).
+  device from ``Broker.shared`` (``emqx_amd.shared_sub.SharedSubs``) in the publish pass itself
+  (``emqxgm_publish_shared_batch``).
 
 The match, aggre and the per-subscriber expansion all run on the device
 (``emqxgm_publish_batch``); this class only maps node / group / subscriber names to the
@@ -124,14 +125,20 @@ class Broker:
     def publish(self, topic: bytes):
         return self.publish_batch([topic])[0]
 
-    def publish_shared_batch(self, topics: Sequence[bytes], messages: Sequence[Tuple]):
+    def publish_shared_batch(self, topics: Sequence[bytes], messages: Sequence[Tuple], fused: bool = True):
         """Per topic the ``{To, Group}`` entries of ``publish_batch`` with the member
         ``emqx_shared_sub:dispatch/3`` sends to: [(To, Group, (status, member, state out, Count))],
         as ``SharedSubs.dispatch_batch`` answers.  messages[i] = (hc, ht, draw, states) of topic i:
         ``erlang:phash2`` of its client id and of its topic, 32 random bits, and the publisher's
-        ``round_robin`` states ``{(Group, To): state}`` (or None)."""
+        ``round_robin`` states ``{(Group, To): state}`` (or None).
+
+        fused (the default): one call, ``emqxgm_publish_shared_batch``, picks on the device in the
+        publish pass itself.  fused=False: the publish, then a second call with the entries packed
+        on the host (``emqxgm_share_pick``); the same answers, kept for the A/B."""
         assert len(messages) == len(topics)
         self.commit()
+        if fused:
+            return self._publish_shared_fused(list(topics), messages)
         res = self.engine.publish(list(topics))
         fb = self.engine.filter_bytes
         reqs, owner = [], []
@@ -145,4 +152,31 @@ class Broker:
         out = [[] for _ in topics]
         for i, r, a in zip(owner, reqs, self.shared.dispatch_batch(reqs) if reqs else []):
             out[i].append((r[1], r[0], a))
+        return out
+
+    def _publish_shared_fused(self, topics, messages):
+        from .shared_sub import STATUS
+        shared = self.shared
+        shared.commit()
+        lookup = self.engine.lookup_id
+        states = []
+        for _, _, _, st in messages:
+            row = []
+            for (group, to), v in (st or {}).items():
+                g, f = self._groups.ids.get(group), lookup(to)
+                if g is not None and f is not None and v is not None:  # (a To that is no filter has no entry)
+                    row.append((g, f, v))
+            states.append(row)
+        res = self.engine.publish_shared(topics, shared.table, [m[0] for m in messages], [m[1] for m in messages],
+                                         [m[2] for m in messages], states)
+        fb = self.engine.filter_bytes
+        out = []
+        for i in range(len(topics)):
+            row = []
+            for (f, d), (m, st, so, count) in zip(res.routes(i), res.shares(i)):
+                if d & DEST_GROUP:
+                    row.append((fb(f), self._groups.names[d & ~DEST_GROUP],
+                                (STATUS[st], None if m == NONE else shared._subs.names[m],
+                                 None if so == NONE else so, count)))
+            out.append(row)
         return out

@@ -675,6 +675,8 @@ int upload_pool(emqxgm* h, PatchList* pl) {
   h->ix.fbytes = (const uint8_t*)h->m_pool.b.p;
   h->ix.foff = (const uint64_t*)h->m_foff.b.p;
   h->ix.fver = (const uint4*)h->m_fver.b.p;
+  h->ix.n_filters = nf;
+  h->ix.pool_bytes = h->pool.size();
   return 0;
 }
 
@@ -923,6 +925,8 @@ void set_tables(DevIndex& to, const DevIndex& from) {
   x.fan_nf = to.fan_nf;
   x.fbytes = to.fbytes;
   x.foff = to.foff;
+  x.n_filters = to.n_filters;
+  x.pool_bytes = to.pool_bytes;
   x.fver = to.fver;
   x.leafp_mask = to.leafp_mask;
   x.psig_off = to.psig_off;
@@ -4221,8 +4225,12 @@ void emqxgm_host_free(emqxgm_t* h, void* p) {
   if (h && p) (void)hipHostFree(p);
 }
 
-int emqxgm_publish_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
-                         emqxgm_publish_out* out) {
+}  // extern "C"
+
+int gm_engine_device(emqxgm_t* h) { return h->cfg.device; }
+
+int gm_publish_hooked(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
+                      emqxgm_publish_out* out, gm_pub_chunk_fn fn, void* ctx) {
   if (!h || !out || (!offsets && n)) return -EINVAL;
   if (int rc = refuse_stale(h)) return rc;
   injected_hang(h);
@@ -4259,10 +4267,17 @@ int emqxgm_publish_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offs
       if (!rc) rc = run_fanout(h, m, &nr, &nd);
       if (rc != 1) break;
     }
-    c.epoch.reset();
-    if (rc) return rc;
     const FanScratch& f = h->fs;
     const uint64_t rbase = h->h_rf.size(), dbase = h->h_df.size();
+    if (!rc && fn && c.epoch) {
+      // the entries where the fill leaves them and the epoch's string pool, before the epoch goes
+      const DevIndex& ix = c.epoch->ix;
+      const gm_pub_chunk ch = {c.stream, i0, m, nr, rbase, f.rp, f.o_rf, f.o_rd, ix.fbytes, ix.foff,
+                               ix.n_filters, ix.pool_bytes};
+      rc = fn(ctx, &ch);
+    }
+    c.epoch.reset();
+    if (rc) return rc;
     h->h_rf.resize(rbase + nr);
     h->h_rd.resize(rbase + nr);
     h->h_df.resize(dbase + nd);
@@ -4294,6 +4309,13 @@ int emqxgm_publish_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offs
   out->deliver_filter = h->h_df.data();
   out->deliver_sub = h->h_ds.data();
   return 0;
+}
+
+extern "C" {
+
+int emqxgm_publish_batch(emqxgm_t* h, const uint8_t* bytes, const uint32_t* offsets, uint32_t n,
+                         emqxgm_publish_out* out) {
+  return gm_publish_hooked(h, bytes, offsets, n, out, nullptr, nullptr);
 }
 
 static int grow_buf(emqxgm* h, DevBuf& b, uint64_t bytes);

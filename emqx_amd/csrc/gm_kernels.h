@@ -34,6 +34,8 @@ struct DevIndex {
   uint64_t xwmask = 0;            // wildcard region bucket count - 1
   const uint8_t* fbytes = nullptr;  // filter string pool
   const uint64_t* foff = nullptr;   // [n_filters+1]
+  uint64_t n_filters = 0;           // filters whose offsets and bytes this index's commit uploaded
+  uint64_t pool_bytes = 0;          //   and the bytes of fbytes they end in
   const uint4* fver = nullptr;      // 64-B verification record per filter id
   const uint32_t* fvbits = nullptr; // bit per filter id: its trie pairs need byte verification
   uint64_t test_mask = 0;           // != 0: collision-test tokens (every word hashed, masked)
@@ -349,17 +351,9 @@ struct AclDbArgs {
   unsigned long long* ctr = nullptr;  // optional: [5] ADB_CTR_*
 };
 hipError_t launch_acldb(const AclDbArgs& a, hipStream_t s);
-// Shared subscriptions (gm_share.inc / gm_share.cpp), device pointers.  One launch per pass of
-// requests against the resident key table and member pool (gm_share_match.h).
-struct ShareArgs {
-  const uint32_t* group = nullptr;  // [n] the request's group
-  const uint8_t* rb = nullptr;      // the pass's topics
-  const uint32_t* ro = nullptr;     // [n+1]
-  const uint32_t* hc = nullptr;     // [n] erlang:phash2(ClientId)
-  const uint32_t* ht = nullptr;     // [n] erlang:phash2(SourceTopic)
-  const uint32_t* draw = nullptr;   // [n] 32 random bits
-  const uint32_t* state = nullptr;  // [n] round_robin state in, NONE for undefined
-  uint32_t n = 0;
+// Shared subscriptions (gm_share.inc / gm_share.cpp), device pointers.  The resident key table and
+// member pool (gm_share_match.h), as both kernels that pick from them take them.
+struct ShareTables {
   const void* tab = nullptr;        // ShSlot table
   uint64_t tmask = 0;               // slots - 1
   const uint32_t* pool = nullptr;   // member pool
@@ -369,11 +363,44 @@ struct ShareArgs {
   const uint32_t* kg = nullptr;     // [n_keys] group of the key
   uint32_t n_keys = 0;
   uint64_t tag_mask = 0;
+};
+// One launch per pass of requests against the tables.
+struct ShareArgs : ShareTables {
+  const uint32_t* group = nullptr;  // [n] the request's group
+  const uint8_t* rb = nullptr;      // the pass's topics
+  const uint32_t* ro = nullptr;     // [n+1]
+  const uint32_t* hc = nullptr;     // [n] erlang:phash2(ClientId)
+  const uint32_t* ht = nullptr;     // [n] erlang:phash2(SourceTopic)
+  const uint32_t* draw = nullptr;   // [n] 32 random bits
+  const uint32_t* state = nullptr;  // [n] round_robin state in, NONE for undefined
+  uint32_t n = 0;
   uint4* out = nullptr;             // [n] {member | NONE, SH_* status, state out, Count | key index}
   uint32_t* err = nullptr;          // set on a key index, run or member position out of bounds
   bool stage = false;               // the block's topics through LDS before hashing
 };
 hipError_t launch_share(const ShareArgs& a, hipStream_t s);
+// The pick of every aggre entry of a publish pass (gm_pubshare.inc), after the fan-out's fill on
+// the same stream: the entries where the fan-out left them, the keys' bytes in the index's
+// string pool, the publishers' round_robin states as a CSR per topic.
+struct PubShareArgs : ShareTables {
+  const uint32_t* rp = nullptr;     // [n+1] FanScratch::rp
+  const uint32_t* o_rf = nullptr;   // [n_routes] entry filter ids
+  const uint32_t* o_rd = nullptr;   // [n_routes] entry dests
+  uint32_t n = 0, n_routes = 0;
+  const uint8_t* fbytes = nullptr;  // DevIndex::fbytes, pool_bytes of them
+  const uint64_t* foff = nullptr;   // [n_filters+1]
+  uint64_t n_filters = 0, pool_bytes = 0;
+  const uint32_t* hc = nullptr;     // [n] per topic, as ShareArgs'
+  const uint32_t* ht = nullptr;
+  const uint32_t* draw = nullptr;
+  const uint32_t* st_ptr = nullptr;     // [n+1] topic t's states are [st_ptr[t], st_ptr[t+1]); NULL: none
+  const uint32_t* st_group = nullptr;   //   group handle
+  const uint32_t* st_filter = nullptr;  //   filter id
+  const uint32_t* st_value = nullptr;   //   the round_robin state
+  uint4* out = nullptr;             // [n_routes] as ShareArgs', or {NONE, SH_NOT_SHARED, NONE, 0}
+  uint32_t* err = nullptr;          // set on anything out of bounds; nothing of it is followed
+};
+hipError_t launch_pubshare(const PubShareArgs& a, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

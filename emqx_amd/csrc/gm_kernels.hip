@@ -205,6 +205,7 @@ __device__ __forceinline__ uint3 stg_load(const uint3* stg, const StgFmt& F, uin
 #include "gm_acl.inc"
 #include "gm_acldb.inc"
 #include "gm_share.inc"
+#include "gm_pubshare.inc"
 
 __global__ __launch_bounds__(WG) void k_row64(const uint32_t* row, uint64_t base, uint64_t* out,
                                               uint32_t m) {
@@ -1253,6 +1254,13 @@ hipError_t launch_share(const ShareArgs& a, hipStream_t s) {
   const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
   if (a.stage) hipLaunchKernelGGL(k_share<true>, grid, dim3(WG), 0, s, a);
   else hipLaunchKernelGGL(k_share<false>, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pubshare(const PubShareArgs& a, hipStream_t s) {
+  if (a.n_routes == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)a.n_routes + WG - 1) / WG));
+  hipLaunchKernelGGL(k_pubshare, grid, dim3(WG), 0, s, a);
   return hipGetLastError();
 }
 

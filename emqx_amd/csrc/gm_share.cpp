@@ -25,7 +25,9 @@
 //
 // The round_robin_per_group counters live here, one per key, and the host takes their step after
 // the device pass (sh_counter_step): requests of one call on one key take consecutive values in
-// request order, with one writer.
+// request order, with one writer.  The handle itself is declared in gm_share_handle.h, which
+// gm_pubshare.cpp (the pick inside the publish pass) shares: it takes the tables, a scratch slot
+// and the counter steps from here (share_tables, share_grow, share_counter_steps).
 //
 // With -DGM_SHARE_EXACT_ALLOC every device array is exactly the bytes in use (no floor, no growth
 // slack): tests/host_harness/share_dev_main.cpp runs this file and the kernel's phases on the CPU
@@ -44,46 +46,12 @@
 #include "../../include/emqx_gpumatch.h"
 #include "gm_common.h"
 #include "gm_kernels.h"
+#include "gm_share_handle.h"
 #include "gm_share_match.h"
 
 using namespace gm;
 
 namespace {
-
-struct ShBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-// A pool: its host mirror, its device array and how many elements of the mirror the device has.
-template <class T>
-struct ShPool {
-  std::vector<T> h;
-  ShBuf d;
-  size_t dev_n = 0;
-};
-
-struct ShTable {
-  std::vector<ShSlot> h;
-  ShBuf d;
-  uint64_t live = 0, tomb = 0;
-  std::vector<uint32_t> touched;  // slots changed since the last upload
-  bool whole = true;              // the device has no copy of this table's size
-};
-
-enum { SH_OP_SUB, SH_OP_UNSUB, SH_OP_DOWN, SH_OP_STRATEGY };
-struct ShOp {
-  uint32_t op = 0, group = 0, sub = 0, arg = 0;  // arg: the local flag or the strategy
-  size_t t0 = 0;                                 // the topic in ptb
-  uint32_t tl = 0;
-};
-
-// What the pending mutations make of one (group, topic, sub): seq orders it against a pending
-// subscriber_down of the sub.
-struct ShTriple {
-  uint32_t seq = 0;
-  int state = -1;  // -1 absent, 0 subscribed remote, 1 subscribed local
-};
 
 // A key a commit touches: its member list and counter as the mutations leave them.
 struct ShWork {
@@ -92,9 +60,6 @@ struct ShWork {
   bool changed = false;
 };
 
-// scratch: the pass's groups, topics, offsets, hc, ht, draw, state, answers; the error word
-enum { SH_GR, SH_RB, SH_RO, SH_HC, SH_HT, SH_DR, SH_ST, SH_OUT, SH_CTL, SH_SLOTS };
-constexpr size_t SH_CTL_BYTES = 8;
 constexpr uint64_t SH_PASS_MAX = 1ull << 28;
 constexpr uint64_t SH_INDEX_MAX = 0xFFFFFFF0ull;  // pool words, keys, key bytes
 constexpr size_t SH_PATCH_MAX = 256;              // touched slots or words beyond this: one copy
@@ -105,43 +70,6 @@ std::string sh_key(uint32_t group, const uint8_t* topic, uint32_t len) {
   if (len) k.append((const char*)topic, len);
   return k;
 }
-
-}  // namespace
-
-struct emqxgm_share {
-  std::mutex mu;
-  int32_t device = 0;
-  hipStream_t stream = nullptr;
-  uint64_t tag_mask = 0;
-  // committed
-  ShTable tab;
-  ShPool<uint32_t> pool, ko, kg;
-  ShPool<uint8_t> kb;
-  std::vector<uint32_t> pool_touched;  // header words rewritten in place since the last upload
-  std::vector<uint32_t> krun;          // per key: its run, NONE once the key is gone (host only)
-  std::vector<uint32_t> ctr;           // per key: the round_robin_per_group counter, NONE if none
-  std::unordered_map<std::string, uint32_t> orphan_ctr;  // counters of keys without members
-  std::unordered_map<uint32_t, uint32_t> gstrat;
-  uint32_t def_strat = SH_ROUND_ROBIN;  // emqx_schema.erl: shared_subscription_strategy
-  uint64_t members = 0, live_words = 0, garbage_words = 0, load_rebuilds = 0, garbage_rebuilds = 0, growths = 0,
-           max_chain = 0;
-  // pending
-  bool broken = false;  // a commit failed half way: the device arrays and the mirror disagree
-  std::vector<ShOp> pend;
-  std::vector<uint8_t> ptb;
-  std::unordered_map<std::string, ShTriple> ptri;
-  std::unordered_map<uint32_t, uint32_t> pdown;
-  // tuning, scratch
-  uint64_t pass_names = 1ull << 20;
-  uint32_t load_pct = 50, garbage_pct = 100;
-  bool timing = false, stage_lds = true;  // MEASUREMENTS.md r16
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double kernel_ms = 0;
-  ShBuf sc[SH_SLOTS];
-  std::vector<uint32_t> h_off;
-};
-
-namespace {
 
 #define SHCHK(expr)                        \
   do {                                     \
@@ -573,8 +501,10 @@ int sh_commit(emqxgm_share* s) {
   return 0;
 }
 
+}  // namespace
+
 // Scratch slot of at least `bytes` (exactly `bytes` with GM_SHARE_EXACT_ALLOC).
-int sh_grow(emqxgm_share* a, int slot, uint64_t bytes) {
+int gm::share_grow(emqxgm_share* a, int slot, uint64_t bytes) {
   ShBuf& b = a->sc[slot];
 #ifdef GM_SHARE_EXACT_ALLOC
   if (b.p && b.bytes == bytes) return 0;
@@ -591,12 +521,49 @@ int sh_grow(emqxgm_share* a, int slot, uint64_t bytes) {
   return 0;
 }
 
+namespace {
+
 int sh_put(emqxgm_share* a, int slot, const void* src, uint64_t bytes) {
-  const int rc = sh_grow(a, slot, bytes);
+  const int rc = share_grow(a, slot, bytes);
   if (rc) return rc;
   if (bytes) SHCHK(hipMemcpyAsync(a->sc[slot].p, src, bytes, hipMemcpyHostToDevice, a->stream));
   return 0;
 }
+
+// The round_robin_per_group steps of the np answers at o, in their order: every
+// SH_COUNTER_PENDING answer takes the next value of its key's counter and becomes a pick.
+}  // namespace
+
+int gm::share_counter_steps(emqxgm_share* a, uint32_t* o, uint64_t np) {
+  for (uint64_t i = 0; i < np; ++i) {
+    uint32_t* r = o + (size_t)i * 4;
+    if (r[1] != SH_COUNTER_PENDING) continue;
+    const uint32_t key = r[3];
+    if (key >= a->krun.size() || a->krun[key] == NONE) return -EIO;
+    const uint32_t run = a->krun[key], count = a->pool.h[run];
+    const uint32_t nth = sh_counter_step(a->ctr[key] == NONE ? 0u : a->ctr[key], count);
+    a->ctr[key] = nth;
+    r[0] = a->pool.h[run + SH_HDR_WORDS + nth - 1] & ~SH_LOCAL_BIT;
+    r[1] = SH_PICKED;
+    r[3] = count;
+  }
+  return 0;
+}
+
+// The committed tables as a kernel takes them.
+void gm::share_tables(const emqxgm_share* a, ShareTables& A) {
+  A.tab = a->tab.d.p;
+  A.tmask = a->tab.h.size() - 1;
+  A.pool = (const uint32_t*)a->pool.d.p;
+  A.pool_words = a->pool.dev_n;
+  A.kb = (const uint8_t*)a->kb.d.p;
+  A.ko = (const uint32_t*)a->ko.d.p;
+  A.kg = (const uint32_t*)a->kg.d.p;
+  A.n_keys = (uint32_t)a->kg.dev_n;
+  A.tag_mask = a->tag_mask;
+}
+
+namespace {
 
 // One pass: requests [lo, hi) of the call; then the host's counter steps, in request order.
 int sh_pass(emqxgm_share* a, const uint32_t* groups, const uint8_t* bytes, const uint32_t* offsets, const uint32_t* hc,
@@ -613,7 +580,7 @@ int sh_pass(emqxgm_share* a, const uint32_t* groups, const uint8_t* bytes, const
       (rc = sh_put(a, SH_RO, a->h_off.data(), ((uint64_t)np + 1) * 4)) ||
       (rc = sh_put(a, SH_HC, hc + lo, (uint64_t)np * 4)) || (rc = sh_put(a, SH_HT, ht + lo, (uint64_t)np * 4)) ||
       (rc = sh_put(a, SH_DR, draw + lo, (uint64_t)np * 4)) || (rc = sh_put(a, SH_ST, state + lo, (uint64_t)np * 4)) ||
-      (rc = sh_grow(a, SH_OUT, (uint64_t)np * 16)) || (rc = sh_grow(a, SH_CTL, SH_CTL_BYTES)))
+      (rc = share_grow(a, SH_OUT, (uint64_t)np * 16)) || (rc = share_grow(a, SH_CTL, SH_CTL_BYTES)))
     return rc;
   auto B = [&](int k) { return a->sc[k].p; };
   SHCHK(hipMemsetAsync(B(SH_CTL), 0, SH_CTL_BYTES, st));
@@ -626,15 +593,7 @@ int sh_pass(emqxgm_share* a, const uint32_t* groups, const uint8_t* bytes, const
   A.draw = (const uint32_t*)B(SH_DR);
   A.state = (const uint32_t*)B(SH_ST);
   A.n = np;
-  A.tab = a->tab.d.p;
-  A.tmask = a->tab.h.size() - 1;
-  A.pool = (const uint32_t*)a->pool.d.p;
-  A.pool_words = a->pool.dev_n;
-  A.kb = (const uint8_t*)a->kb.d.p;
-  A.ko = (const uint32_t*)a->ko.d.p;
-  A.kg = (const uint32_t*)a->kg.d.p;
-  A.n_keys = (uint32_t)a->kg.dev_n;
-  A.tag_mask = a->tag_mask;
+  share_tables(a, A);
   A.out = (uint4*)B(SH_OUT);
   A.err = (uint32_t*)B(SH_CTL);
   A.stage = a->stage_lds;
@@ -653,19 +612,7 @@ int sh_pass(emqxgm_share* a, const uint32_t* groups, const uint8_t* bytes, const
     SHCHK(hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
     a->kernel_ms += ms;
   }
-  for (uint32_t i = 0; i < np; ++i) {
-    uint32_t* r = o + (size_t)i * 4;
-    if (r[1] != SH_COUNTER_PENDING) continue;
-    const uint32_t key = r[3];
-    if (key >= a->krun.size() || a->krun[key] == NONE) return -EIO;
-    const uint32_t run = a->krun[key], count = a->pool.h[run];
-    const uint32_t nth = sh_counter_step(a->ctr[key] == NONE ? 0u : a->ctr[key], count);
-    a->ctr[key] = nth;
-    r[0] = a->pool.h[run + SH_HDR_WORDS + nth - 1] & ~SH_LOCAL_BIT;
-    r[1] = SH_PICKED;
-    r[3] = count;
-  }
-  return 0;
+  return share_counter_steps(a, o, np);
 }
 
 }  // namespace

@@ -20,6 +20,10 @@
 // barriers and nothing else; tests/host_harness/share_dev_main.cpp runs each phase for all WG
 // lanes of a block before the next, under ASan + UBSan.  No atomics, no block waits for another;
 // LDS holds the staged topic bytes and nothing else.
+//
+// The probe, the header, the decision and the member load are written over a key given as pointer
+// and length (sh_probe_key .. sh_member_answer): k_share's phases call them with the request's
+// bytes, k_pubshare's (gm_pubshare.inc) with a filter's bytes in the index's string pool.
 
 struct ShLane {
   uint32_t t, active;
@@ -41,15 +45,71 @@ __device__ __forceinline__ void sh_ph_stage(const ShareArgs& A, uint8_t* s_keys)
   for (uint32_t i = threadIdx.x; i < nb; i += WG) s_keys[i] = A.rb[b0 + i];
 }
 
-__device__ __forceinline__ void sh_ph_hash(const ShareArgs& A, ShLane& L, const uint8_t* s_keys) {
-  L.t = blockIdx.x * WG + threadIdx.x;
-  L.active = L.t < A.n;
+// ---- the phase bodies over a key given as pointer and length: k_share's phases below and
+// k_pubshare's (gm_pubshare.inc) call these, so a pick is decided by one copy of the code ----
+
+__device__ __forceinline__ void sh_lane_reset(ShLane& L) {
+  L.t = L.active = 0;
   L.group = L.k0 = L.kl = 0;
   L.tag = 0;
   L.run = L.key = NONE;
   L.n_all = L.n_local = L.strategy = 0;
   L.d = ShDecision{SH_NO_SUBSCRIBERS, 0, NONE};
   L.bad = 0;
+}
+
+// The slot of (L.group, key bytes) by L.tag: L.run and L.key, or both NONE.
+__device__ __forceinline__ void sh_probe_key(const ShareTables& T, ShLane& L, const uint8_t* key, uint32_t len) {
+  const ShSlot* tab = (const ShSlot*)T.tab;
+  uint64_t i = sh_home(L.tag, T.tmask), steps = 0;
+  uint32_t at;
+  while ((at = sh_probe_next(tab, T.tmask, L.tag, &i, &steps)) != NONE) {
+    const uint32_t k = tab[at].key;
+    if (k >= T.n_keys) {  // never followed
+      L.bad = 1;
+      return;
+    }
+    if (sh_confirm(T.kg, T.ko, T.kb, k, L.group, key, len)) break;
+  }
+  if (at == NONE) return;
+  L.run = tab[at].run;
+  L.key = tab[at].key;
+}
+
+__device__ __forceinline__ void sh_header_run(const ShareTables& T, ShLane& L) {
+  if (!sh_read_run(T.pool, T.pool_words, L.run, &L.n_all, &L.n_local, &L.strategy)) {
+    L.bad = 1;
+    L.run = NONE;
+  }
+}
+
+__device__ __forceinline__ void sh_decide_run(ShLane& L, uint32_t hc, uint32_t ht, uint32_t draw) {
+  L.d = sh_decide(L.n_all, L.n_local, L.strategy, hc, ht, draw, L.d.state);
+  if (L.d.status == SH_MALFORMED) L.bad = 1;
+}
+
+// The bounds check of the member position, the error word, and an active lane's answer.
+__device__ __forceinline__ uint4 sh_member_answer(const ShareTables& T, ShLane& L, uint32_t* err) {
+  if (L.active && !L.bad && L.run != NONE && L.d.status == SH_PICKED &&
+      L.d.pos >= sh_run_words(L.n_all, L.n_local))
+    L.bad = 1;  // a member position past the run: never followed
+  if (L.bad) *err = 1u;
+  uint32_t member = NONE, aux = L.n_all;
+  if (L.bad) {
+    L.d.status = SH_MALFORMED;
+  } else if (L.active && L.run != NONE) {
+    if (L.d.status == SH_PICKED) member = T.pool[L.run + L.d.pos] & ~SH_LOCAL_BIT;
+    if (L.d.status == SH_COUNTER_PENDING) aux = L.key;
+  }
+  return make_uint4(member, L.d.status, L.d.state, aux);
+}
+
+// ---- k_share's phases ----
+
+__device__ __forceinline__ void sh_ph_hash(const ShareArgs& A, ShLane& L, const uint8_t* s_keys) {
+  sh_lane_reset(L);
+  L.t = blockIdx.x * WG + threadIdx.x;
+  L.active = L.t < A.n;
   if (!L.active) return;
   L.group = A.group[L.t];
   L.k0 = A.ro[L.t];
@@ -63,50 +123,22 @@ __device__ __forceinline__ void sh_ph_hash(const ShareArgs& A, ShLane& L, const 
 
 __device__ __forceinline__ void sh_ph_probe(const ShareArgs& A, ShLane& L) {
   if (!L.active) return;
-  const ShSlot* tab = (const ShSlot*)A.tab;
-  uint64_t i = sh_home(L.tag, A.tmask), steps = 0;
-  uint32_t at;
-  while ((at = sh_probe_next(tab, A.tmask, L.tag, &i, &steps)) != NONE) {
-    const uint32_t key = tab[at].key;
-    if (key >= A.n_keys) {  // never followed
-      L.bad = 1;
-      return;
-    }
-    if (sh_confirm(A.kg, A.ko, A.kb, key, L.group, A.rb + L.k0, L.kl)) break;
-  }
-  if (at == NONE) return;
-  L.run = tab[at].run;
-  L.key = tab[at].key;
+  sh_probe_key(A, L, A.rb + L.k0, L.kl);
 }
 
 __device__ __forceinline__ void sh_ph_header(const ShareArgs& A, ShLane& L) {
   if (!L.active || L.bad || L.run == NONE) return;
-  if (!sh_read_run(A.pool, A.pool_words, L.run, &L.n_all, &L.n_local, &L.strategy)) {
-    L.bad = 1;
-    L.run = NONE;
-  }
+  sh_header_run(A, L);
 }
 
 __device__ __forceinline__ void sh_ph_decide(const ShareArgs& A, ShLane& L) {
   if (!L.active || L.bad || L.run == NONE) return;
-  L.d = sh_decide(L.n_all, L.n_local, L.strategy, A.hc[L.t], A.ht[L.t], A.draw[L.t], L.d.state);
-  if (L.d.status == SH_MALFORMED) L.bad = 1;
+  sh_decide_run(L, A.hc[L.t], A.ht[L.t], A.draw[L.t]);
 }
 
 __device__ __forceinline__ void sh_ph_member(const ShareArgs& A, ShLane& L) {
-  if (L.active && !L.bad && L.run != NONE && L.d.status == SH_PICKED &&
-      L.d.pos >= sh_run_words(L.n_all, L.n_local))
-    L.bad = 1;  // a member position past the run: never followed
-  if (L.bad) *A.err = 1u;
-  if (!L.active) return;
-  uint32_t member = NONE, aux = L.n_all;
-  if (L.bad) {
-    L.d.status = SH_MALFORMED;
-  } else if (L.run != NONE) {
-    if (L.d.status == SH_PICKED) member = A.pool[L.run + L.d.pos] & ~SH_LOCAL_BIT;
-    if (L.d.status == SH_COUNTER_PENDING) aux = L.key;
-  }
-  A.out[L.t] = make_uint4(member, L.d.status, L.d.state, aux);
+  const uint4 r = sh_member_answer(A, L, A.err);
+  if (L.active) A.out[L.t] = r;
 }
 
 template <bool STAGE>

@@ -33,8 +33,10 @@ constexpr uint32_t SH_RANDOM = 0, SH_ROUND_ROBIN = 1, SH_RR_PER_GROUP = 2, SH_ST
                    SH_HASH_CLIENTID = 5, SH_HASH_TOPIC = 6, SH_STRATEGIES = 7;
 // ... and the status of an answer
 constexpr uint32_t SH_PICKED = 0, SH_NO_SUBSCRIBERS = 1, SH_HOST_STRATEGY = 2, SH_COUNTER_PENDING = 3,
-                   SH_MALFORMED = 4;  // (never leaves the library: the call returns -EIO)
+                   SH_MALFORMED = 4,  // (never leaves the library: the call returns -EIO)
+                   SH_NOT_SHARED = 5;  // k_pubshare: the entry's dest is a node, nothing was picked
 constexpr uint32_t SH_LOCAL_BIT = 1u << 31;
+constexpr uint32_t DEST_GROUP_BIT = 1u << 31;  // EMQXGM_DEST_GROUP: the dest of an aggre entry is a group
 constexpr uint32_t SH_HDR_WORDS = 4;
 constexpr uint64_t SH_EMPTY = 1ull << 63;
 constexpr uint64_t SH_DELETED = (1ull << 63) | 1ull;

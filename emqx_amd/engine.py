@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 11  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 12  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -50,6 +50,10 @@ class _PubOut(C.Structure):
                 ("route_dest", C.POINTER(C.c_uint32)), ("deliver_ptr", C.POINTER(C.c_uint64)),
                 ("deliver_filter", C.POINTER(C.c_uint32)),
                 ("deliver_sub", C.POINTER(C.c_uint32))]
+
+
+class _PubSharedOut(C.Structure):  # emqxgm_publish_shared_out
+    _fields_ = [("pub", _PubOut), ("share", C.POINTER(C.c_uint32))]
 
 
 class _BatchOut(C.Structure):
@@ -251,6 +255,8 @@ SYMBOLS = {
     "emqxgm_share_set_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "emqxgm_share_commit": (C.c_int, [_P]),
     "emqxgm_share_pick": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "emqxgm_publish_shared_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
+                                              C.POINTER(_PubSharedOut)]),
     "emqxgm_share_members": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _U32P]),
     "emqxgm_share_counter": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _U32P]),
     "emqxgm_share_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
@@ -340,6 +346,7 @@ class PublishResult:
     deliver_ptr: np.ndarray    # uint64 [n+1]
     deliver_filter: np.ndarray
     deliver_sub: np.ndarray
+    share: Optional[np.ndarray] = None  # uint32 [n_routes, 4] (publish_shared only)
 
     def routes(self, i: int):
         a, b = int(self.route_ptr[i]), int(self.route_ptr[i + 1])
@@ -348,6 +355,12 @@ class PublishResult:
     def deliveries(self, i: int):
         a, b = int(self.deliver_ptr[i]), int(self.deliver_ptr[i + 1])
         return list(zip(self.deliver_filter[a:b].tolist(), self.deliver_sub[a:b].tolist()))
+
+    def shares(self, i: int):
+        """Topic i's quadruples (member | NONE, SHARE_* status, state out, Count), one per entry of
+        routes(i) and in its order; SHARE_NOT_SHARED for an entry whose dest is a node."""
+        a, b = int(self.route_ptr[i]), int(self.route_ptr[i + 1])
+        return [tuple(r) for r in self.share[a:b].tolist()]
 
 
 @dataclass
@@ -518,6 +531,10 @@ class Engine:
         self._check(self._lib.emqxgm_publish_batch(self._h, _ptr(buf), _ptr(off32), n,
                                                    C.byref(o)), "publish_batch")
 
+        return self._publish_result(o, n)
+
+    @staticmethod
+    def _publish_result(o: _PubOut, n: int, share=None) -> PublishResult:
         def arr(p, k, dt):
             return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dt)
         return PublishResult(arr(o.route_ptr, n + 1, np.uint64),
@@ -525,7 +542,40 @@ class Engine:
                              arr(o.route_dest, o.n_routes, np.uint32),
                              arr(o.deliver_ptr, n + 1, np.uint64),
                              arr(o.deliver_filter, o.n_deliveries, np.uint32),
-                             arr(o.deliver_sub, o.n_deliveries, np.uint32))
+                             arr(o.deliver_sub, o.n_deliveries, np.uint32),
+                             None if share is None else arr(share, 4 * o.n_routes, np.uint32).reshape(-1, 4))
+
+    def publish_shared(self, topics: Sequence[bytes], share: "SharedSub", hc, ht, draw,
+                       states=None) -> PublishResult:
+        """emqxgm_publish_shared_batch: publish() plus, per aggre entry, the member
+        emqx_shared_sub:dispatch/3 picks from `share` (shares(i)), in one device pass.  hc, ht, draw:
+        per topic, as SharedSub.pick's.  states: per topic the publisher's round_robin states as a
+        list of (group handle, filter id, value); None: every state is undefined."""
+        topics = list(topics)
+        buf, off = pack(topics, np.uint64)
+        if len(buf) > 0xFFFFFFFF:
+            raise EngineError("batch larger than 4 GiB: split it")
+        off32 = np.ascontiguousarray(off, dtype=np.uint32)
+        n = len(topics)
+        per = [np.ascontiguousarray(np.asarray(a, np.uint64).astype(np.uint32)) for a in (hc, ht, draw)]
+        assert all(len(a) == n for a in per)
+        sp = sg = sf = sv = None
+        if states is not None:
+            assert len(states) == n
+            flat = [t for st in states for t in st]
+            sp = np.zeros(n + 1, np.uint32)
+            np.cumsum([len(st) for st in states], out=sp[1:])
+            sg, sf, sv = (np.ascontiguousarray(np.asarray([t[k] for t in flat], np.uint64).astype(np.uint32))
+                          for k in range(3))
+        o = _PubSharedOut()
+
+        def ptr(a):
+            return C.c_void_p(0) if a is None else _ptr(a)
+        self._check(self._lib.emqxgm_publish_shared_batch(
+            self._h, share._h, _ptr(buf), off32.ctypes.data_as(C.c_void_p), n, _ptr(per[0]), _ptr(per[1]),
+            _ptr(per[2]), None if sp is None else sp.ctypes.data_as(C.c_void_p), ptr(sg), ptr(sf), ptr(sv),
+            C.byref(o)), "publish_shared_batch")
+        return self._publish_result(o.pub, n, o.share)
 
     def trie_insert_many(self, buf: np.ndarray, off: np.ndarray) -> np.ndarray:
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -1285,6 +1335,7 @@ class AclDb:
 SHARE_STRATEGIES = ("random", "round_robin", "round_robin_per_group", "sticky", "local", "hash_clientid",
                     "hash_topic")
 SHARE_PICKED, SHARE_NO_SUBSCRIBERS, SHARE_HOST_STRATEGY = 0, 1, 2
+SHARE_NOT_SHARED = 5  # emqxgm_publish_shared_batch: an entry whose dest is a node
 SHARE_LOCAL_MEMBER = 0x80000000
 SHARE_STAT_KEYS = ("keys", "slots", "deleted", "max_chain", "members", "live_words", "garbage_words",
                    "load_rebuilds", "garbage_rebuilds", "growths", "counters", "pending")

@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 11
+#define EMQXGM_ABI_VERSION 12
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -747,6 +747,34 @@ int emqxgm_share_commit(emqxgm_share_t* s);
 int emqxgm_share_pick(emqxgm_share_t* s, uint32_t n, const uint32_t* groups, const uint8_t* key_bytes,
                       const uint32_t* key_offsets, const uint32_t* hc, const uint32_t* ht,
                       const uint32_t* draw, const uint32_t* state, uint32_t* out);
+/* emqx_broker:publish/1 through route/2 for a batch of topics (emqx_broker.erl:262-282): what
+ * emqxgm_publish_batch answers, and for every aggre/1 entry of it the member that
+ * emqx_shared_sub:dispatch/3 sends a {To, Group} entry to (emqx_shared_sub.erl:138-157, 309-379),
+ * picked in the same device pass against the index epoch the match and the fan-out read.  The key
+ * of entry j is (route_dest[j] without EMQXGM_DEST_GROUP, the bytes of filter route_filter[j]).
+ * hc[i], ht[i] and draw[i] are topic i's, as emqxgm_share_pick's.  The publisher's round_robin
+ * states of topic i (its process dictionary, :365-372, passed whole) are the triples
+ * [st_ptr[i], st_ptr[i+1]) of (st_group, st_filter, st_value): group handle, filter id of To,
+ * state; the first pair that matches an entry is its state in, no match is undefined; st_ptr NULL:
+ * every state is undefined.  out->pub is exactly emqxgm_publish_batch's answer; out->share holds
+ * four words per entry, in the entries' order, with emqxgm_share_pick's meaning, and
+ * {EMQXGM_NONE, EMQXGM_SHARE_NOT_SHARED, EMQXGM_NONE, 0} for an entry whose dest is a node.  It
+ * stays valid until the next call with s.  round_robin_per_group entries of one call on one key
+ * take consecutive counter values in entry order (topic order, then the entries of a topic).
+ * -EINVAL, before anything is launched, on a null handle or per-topic array, handles on different
+ * devices, non-monotone offsets or st_ptr, or a st_group >= 2^31; -ESTALE as emqxgm_publish_batch;
+ * -EIO when the share handle is broken or a lane found a malformed table, run or string-pool
+ * range.  Locks: the engine's, then the share handle's, held to the end of the counter steps. */
+#define EMQXGM_SHARE_NOT_SHARED 5u /* status of an entry whose dest is a node */
+typedef struct emqxgm_publish_shared_out {
+  emqxgm_publish_out pub; /* exactly what emqxgm_publish_batch answers */
+  const uint32_t* share;  /* [4 * pub.n_routes], entry j at share[4j..4j+3] */
+} emqxgm_publish_shared_out;
+int emqxgm_publish_shared_batch(emqxgm_t* h, emqxgm_share_t* s, const uint8_t* bytes,
+                                const uint32_t* offsets, uint32_t n, const uint32_t* hc,
+                                const uint32_t* ht, const uint32_t* draw, const uint32_t* st_ptr,
+                                const uint32_t* st_group, const uint32_t* st_filter,
+                                const uint32_t* st_value, emqxgm_publish_shared_out* out);
 /* subscribers/2 (:391-392): *n_out = the committed members of (group, topic), the first
  * min(cap, *n_out) into out in order, EMQXGM_SHARE_LOCAL_MEMBER set on the local ones.  From the
  * host mirror: no device call. */
