@@ -7,6 +7,7 @@ The product is ``libemqx_gpumatch.so`` (gfx950 HIP kernels + host index builder 
     from emqx_amd import Trie, Router, Broker, Engine
 """
 from . import authz  # noqa: F401
+from .admission import Admission  # noqa: F401
 from .authz import AclList, BuiltinDb, InvalidRule  # noqa: F401
 from .broker import Broker  # noqa: F401
 from .engine import NONE, Acl, AclDb, SharedSub, AsyncMatcher, AsyncResult, Batcher, DeviceResult, Engine, EngineError, MatchResult, PublishResult, Window  # noqa: F401
@@ -19,6 +20,6 @@ from .trie import Trie  # noqa: F401
 
 __all__ = ["Engine", "EngineError", "MatchResult", "DeviceResult", "PublishResult", "Trie",
            "Router", "SessionRouter", "Broker", "TopicRules", "RuleSet", "Acl", "AclList", "authz",
-           "AclDb", "BuiltinDb", "InvalidRule", "SharedSub", "SharedSubs",
+           "AclDb", "BuiltinDb", "InvalidRule", "SharedSub", "SharedSubs", "Admission",
            "get_rules_for_topic", "get_matched_egress_bridges", "Retainer", "Batcher", "Window",
            "AsyncMatcher", "AsyncResult", "NONE"]

@@ -28,7 +28,7 @@ WORKLOAD_SO = os.path.join(ROOT, "workloads", "libemqx_workload.so")
 LOAD_SO = os.path.join(ROOT, "tests", "host_harness", "lib", "libasync_load.so")
 NIF_DRIVER = os.path.join(ROOT, "tests", "host_harness", "lib", "nif_driver")
 
-ENGINE_SRCS = ["gm_kernels.hip", "gm_engine.cpp", "gm_retain.cpp", "gm_ruleset.cpp", "gm_acl.cpp", "gm_acldb.cpp", "gm_share.cpp", "gm_pubshare.cpp", "gm_batcher.cpp", "gm_async.cpp"]
+ENGINE_SRCS = ["gm_kernels.hip", "gm_engine.cpp", "gm_retain.cpp", "gm_ruleset.cpp", "gm_acl.cpp", "gm_acldb.cpp", "gm_share.cpp", "gm_pubshare.cpp", "gm_admit.cpp", "gm_batcher.cpp", "gm_async.cpp"]
 ENGINE_DEPS = sorted(set(ENGINE_SRCS) | {f for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))})
 
 

@@ -401,6 +401,23 @@ struct PubShareArgs : ShareTables {
   uint32_t* err = nullptr;          // set on anything out of bounds; nothing of it is followed
 };
 hipError_t launch_pubshare(const PubShareArgs& a, hipStream_t s);
+// One admission pass (gm_admit.inc): n items of one mode, their packed bytes, per-item flags and
+// zones, the zones' caps as {max_topic_levels, max_qos_allowed | ADM_C_* bits} (gm_admit_match.h).
+struct AdmitArgs {
+  const uint8_t* bytes = nullptr;  // the pass's bytes; readable over the 16-B chunks that hold them
+  const uint32_t* off = nullptr;   // [n+1]
+  uint32_t n = 0;
+  uint32_t nbytes = 0;                // off[n]: no offset beyond it is followed
+  uint32_t mode = 0;                  // ADM_NAME | ADM_FILTER
+  const uint8_t* in_flags = nullptr;  // [n] qos | retain | HAS_SHARE, or null: all 0
+  const uint8_t* zone = nullptr;      // [n] row of caps, or null: row 0
+  const uint2* caps = nullptr;        // [n_zones]
+  uint32_t n_zones = 0;
+  uint4* out = nullptr;     // [n] the records
+  uint32_t* err = nullptr;  // set on an offset or a zone out of bounds
+  bool force_global = false;  // no LDS tile: every item from global memory
+};
+hipError_t launch_admit(const AdmitArgs& a, hipStream_t s);
 // One patch of a delta commit: w (1..64) dwords from src[s..] to the device address dst.
 struct PatchEnt {
   uint64_t dst;

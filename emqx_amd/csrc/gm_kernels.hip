@@ -18,6 +18,7 @@
 #include "gm_acl_match.h"
 #include "gm_acldb_match.h"
 #include "gm_share_match.h"
+#include "gm_admit_match.h"
 
 namespace gm {
 
@@ -206,6 +207,7 @@ __device__ __forceinline__ uint3 stg_load(const uint3* stg, const StgFmt& F, uin
 #include "gm_acldb.inc"
 #include "gm_share.inc"
 #include "gm_pubshare.inc"
+#include "gm_admit.inc"
 
 __global__ __launch_bounds__(WG) void k_row64(const uint32_t* row, uint64_t base, uint64_t* out,
                                               uint32_t m) {
@@ -1261,6 +1263,13 @@ hipError_t launch_pubshare(const PubShareArgs& a, hipStream_t s) {
   if (a.n_routes == 0) return hipSuccess;
   const dim3 grid((uint32_t)(((uint64_t)a.n_routes + WG - 1) / WG));
   hipLaunchKernelGGL(k_pubshare, grid, dim3(WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_admit(const AdmitArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const dim3 grid((uint32_t)(((uint64_t)a.n + WG - 1) / WG));
+  hipLaunchKernelGGL(k_admit, grid, dim3(WG), 0, s, a);
   return hipGetLastError();
 }
 

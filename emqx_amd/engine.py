@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libemqx_gpumatch.so")
 NONE = 0xFFFFFFFF
-ABI_VERSION = 12  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
+ABI_VERSION = 13  # include/emqx_gpumatch.h EMQXGM_ABI_VERSION
 SET_COMMIT = 1  # EMQXGM_SET_COMMIT
 TAG_CANCELLED = 0xFFFFFFFFFFFFFFFF  # EMQXGM_TAG_CANCELLED
 
@@ -261,6 +261,13 @@ SYMBOLS = {
     "emqxgm_share_counter": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _U32P]),
     "emqxgm_share_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "emqxgm_share_stats": (C.c_int, [_P, _U64P]),
+    "emqxgm_admit_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
+    "emqxgm_admit_destroy": (None, [_P]),
+    "emqxgm_admit_batch": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32,
+                                     C.POINTER(_U32P)]),
+    "emqxgm_admit_reason": (C.c_uint32, [C.c_uint32, _P]),
+    "emqxgm_admit_tune": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emqxgm_admit_stats": (C.c_int, [_P, _U64P]),
     "emqxgm_batcher_create": (C.c_int, [_P, C.POINTER(_BatcherCfg), C.POINTER(_P)]),
     "emqxgm_batcher_destroy": (None, [_P]),
     "emqxgm_batcher_add": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, _U32P]),

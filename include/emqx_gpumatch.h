@@ -79,7 +79,7 @@ extern "C" {
 #define EMQXGM_DEST_GROUP 0x80000000u /* dest handle bit: a shared-subscription group */
 #define EMQXGM_RULE_EQ 1u    /* rule flag: {eq, Filter} -- the name must equal the filter */
 #define EMQXGM_RULE_WORDS 2u /* rule flag: match/2 on word lists (no '$' clauses) */
-#define EMQXGM_ABI_VERSION 12
+#define EMQXGM_ABI_VERSION 13
 #define EMQXGM_SET_COMMIT 1u /* emqxgm_route_set_batch: visible before the call returns */
 
 typedef struct emqxgm emqxgm_t;
@@ -792,6 +792,91 @@ int emqxgm_share_tune(emqxgm_share_t* s, const char* key, int64_t value);
  * pool words, garbage words, rebuilds forced by the table's load, rebuilds forced by garbage, pool
  * growths, counters held, pending mutations} */
 int emqxgm_share_stats(emqxgm_share_t* s, uint64_t out[12]);
+
+/* ---- admission: validate/2, parse/1 and the caps checks per name or filter -----------------
+ * The steps of the channel in front of the match, for a batch of PUBLISH topic names or SUBSCRIBE
+ * topic filters, on their raw bytes (any bytes: nothing is assumed to be UTF-8):
+ *   EMQXGM_ADMIT_NAME    emqx_packet:check/1 -> emqx_topic:validate(name, Topic)
+ *                        (apps/emqx/src/emqx_packet.erl:254-260, emqx_topic.erl:98-130), then
+ *                        emqx_mqtt_caps:check_pub/2 (emqx_channel.erl:647,1850-1860,
+ *                        emqx_mqtt_caps.erl:74-105);
+ *   EMQXGM_ADMIT_FILTER  validate_topic_filters (emqx_packet.erl:267-273,411-420), then
+ *                        emqx_topic:parse/1 (emqx_channel.erl:510,2087-2089,
+ *                        emqx_topic.erl:206-233), then emqx_mqtt_caps:check_sub/3
+ *                        (emqx_channel.erl:801,1885-1886, emqx_mqtt_caps.erl:107-152).
+ * Stateless: a handle owns a stream and scratch only.  Per item one record of four words:
+ *   rec[0]  validate verdict (EMQXGM_ADMIT_V_*) | parse verdict << 8 (0 ok, 1
+ *           {invalid_topic_filter, _}) | caps reason code << 16 (0 ok, else the reference's byte,
+ *           emqx_mqtt.hrl:173-192) | EMQXGM_ADMIT_WILDCARD | _SHARED | _EXCLUSIVE | _EXCL_LOOKUP
+ *   rec[1]  levels/1 of the name, or of the topic parse/1 returned
+ *   rec[2]  byte offset of the topic parse/1 returned inside the item (0 for a name)
+ *   rec[3]  length of the share name parse/1 took from the string (it starts at byte 7), or
+ *           EMQXGM_NONE
+ * The three results are independent: parse is reported whatever validate said (NAME: 0), and the
+ * caps are checked on the parsed topic whatever validate said.  validate is of the raw item.  A
+ * sequence that <<_/utf8>> does not accept (RFC 3629: overlong forms, surrogates, above U+10FFFF,
+ * lone continuation bytes, truncated sequences) in a word validate3 examines is
+ * EMQXGM_ADMIT_V_FUNCTION_CLAUSE, as the reference ends in function_clause there.  For an item
+ * whose parse failed, rec[1] and rec[2] are 0, rec[3] EMQXGM_NONE and no caps reason or flag is
+ * set; for an item of more than 65535 bytes levels, wildcard and caps are not run (rec[1] 0, no
+ * reason, no _WILDCARD or _EXCL_LOOKUP) and parse's answer stands (rec[2], rec[3], _SHARED,
+ * _EXCLUSIVE).  EMQXGM_ADMIT_SHARED: the options carry `share` (from the string
+ * or from EMQXGM_ADMIT_IN_HAS_SHARE).  EMQXGM_ADMIT_EXCL_LOOKUP: the zone has
+ * exclusive_subscription and the filter is exclusive -- the reference asks
+ * emqx_exclusive_subscription:check_subscribe/2 (emqx_mqtt_caps.erl:144-150), the caller must. */
+#define EMQXGM_ADMIT_NAME 0u
+#define EMQXGM_ADMIT_FILTER 1u
+#define EMQXGM_ADMIT_V_OK 0u
+#define EMQXGM_ADMIT_V_EMPTY_TOPIC 1u
+#define EMQXGM_ADMIT_V_TOO_LONG 2u
+#define EMQXGM_ADMIT_V_NAME_ERROR 3u
+#define EMQXGM_ADMIT_V_INVALID_HASH 4u /* 'topic_invalid_#' */
+#define EMQXGM_ADMIT_V_INVALID_CHAR 5u
+#define EMQXGM_ADMIT_V_FUNCTION_CLAUSE 6u
+#define EMQXGM_ADMIT_WILDCARD (1u << 24)
+#define EMQXGM_ADMIT_SHARED (1u << 25)
+#define EMQXGM_ADMIT_EXCLUSIVE (1u << 26)
+#define EMQXGM_ADMIT_EXCL_LOOKUP (1u << 27)
+#define EMQXGM_ADMIT_IN_RETAIN 4u    /* in_flags: bits 0-1 are the QoS */
+#define EMQXGM_ADMIT_IN_HAS_SHARE 8u /* in_flags: the options passed to parse/1 carry `share` */
+#define EMQXGM_ADMIT_RAISES 0x100u   /* emqxgm_admit_reason: parse/1 raises inside handle_in */
+#define EMQXGM_ADMIT_MAX_ZONES 256u
+/* A zone's caps (emqx_mqtt_caps.erl:61-72 has the defaults: 65535, 2, true, true, true, false;
+ * max_topic_levels 0 = no limit, :94-96). */
+typedef struct emqxgm_admit_caps {
+  uint32_t max_topic_levels;
+  uint8_t max_qos_allowed;
+  uint8_t retain_available;
+  uint8_t wildcard_subscription;
+  uint8_t shared_subscription;
+  uint8_t exclusive_subscription;
+  uint8_t reserved[3];
+} emqxgm_admit_caps;
+typedef struct emqxgm_admit emqxgm_admit_t;
+int emqxgm_admit_create(int32_t device, emqxgm_admit_t** out);
+void emqxgm_admit_destroy(emqxgm_admit_t* a);
+/* One batch of n items of one mode: item i is bytes[offsets[i] .. offsets[i+1]) (host memory).
+ * in_flags[i] (null: all 0) = QoS | EMQXGM_ADMIT_IN_RETAIN | EMQXGM_ADMIT_IN_HAS_SHARE; zone[i]
+ * (null: all 0) = the row of caps[n_zones] (1..256 rows) the item is checked against.  *out = the
+ * records, four words per item, in host memory of the handle, valid until the next call on a.
+ * Larger batches are cut into passes internally.  -EINVAL, before anything is launched, on
+ * decreasing offsets, a zone >= n_zones, n_zones out of range or a max_qos_allowed above 2; -EIO
+ * when a device call failed or a lane found an offset or zone out of bounds. */
+int emqxgm_admit_batch(emqxgm_admit_t* a, uint32_t mode, const uint8_t* bytes,
+                       const uint32_t* offsets, uint32_t n, const uint8_t* in_flags,
+                       const uint8_t* zone, const emqxgm_admit_caps* caps, uint32_t n_zones,
+                       const uint32_t** out);
+/* The first failure in the order the channel takes them, from one record: NAME: any validate
+ * error is 16#90 (emqx_channel.erl:647 after emqx_packet:check/1), then the caps reason; FILTER:
+ * any validate error is 16#8F, then EMQXGM_ADMIT_RAISES for a parse failure, then the caps
+ * reason; 0 = admitted.  No device call. */
+uint32_t emqxgm_admit_reason(uint32_t mode, const uint32_t* rec);
+/* "pass_items" (items per launch), "timing" and the read-only "kernel_us" as emqxgm_acl_tune;
+ * "force_global" (1: no LDS tile, every item is read from global memory; same records);
+ * "byte_base" (0..15, tests: the residue of a pass's first byte in its 16-B chunk). */
+int emqxgm_admit_tune(emqxgm_admit_t* a, const char* key, int64_t value);
+/* out = {calls, items, bytes, passes, scratch growths, kernel microseconds (timing on)} */
+int emqxgm_admit_stats(emqxgm_admit_t* a, uint64_t out[6]);
 
 /* ---- single-driver batcher core: publish windows over the host pipes ---------------------
  * A caller that batches topics itself (one thread adding, flushing and collecting; bench.py's
